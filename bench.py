@@ -2,7 +2,7 @@
 """Benchmark: SDF+grad point-evals/s, 1M-point cloud x 64-primitive model (M64).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config m64|c2|c4]
-                    [--points P | --global-points G]
+                    [--points P | --global-points G] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 A step is ONE residual pass of the hot path over the resident cloud: the pose
@@ -10,20 +10,27 @@ kernel (the 12·S pose doubles ride in its arguments), the pass kernel (per
 point: nearest hull d*, k*, ∇d* written to HBM + the cost/wrench partial sums),
 the fixed-order reduce kernel and, for N > 1, the RCCL all-reduce of the
 1+6S-double accumulator. Steps run one pass at a time (the
-headline `value`), as a track! iteration does; at N = 1 the line also carries
-the dependent step (pass + accumulator read-back + host wait, every step) and,
-labelled as such, the aggregate of two independent passes in flight
-(config.inflight_throughput).
+headline `value`), as a track! iteration does.
+
+A plain run does what the headline needs and no more: it sets up (model, cloud,
+upload, the frame's regroup, the settle), runs the W warmup steps, times the K
+steps, writes the last step's outputs if --dump-outputs is given and prints the
+line (`value`, `ms_per_step`, the static `config`, the roofline from the timed
+region's own kernel events). Everything else is measured only with --full: at
+N = 1 the dependent step (pass + accumulator read-back + host wait, every step)
+and, labelled as such, the aggregate of two independent passes in flight
+(config.inflight_throughput); for W > 1 the other scaling figure, the ingest and
+the all-reduce on its own; and the blocks marked (--full) below.
 
 Sharding (contiguous point ranges, uploaded once per frame):
   (default)           weak scaling of the metric's cloud (`value`): every rank
                       its own 2^20-point M64 cloud (rank r seeded seed+17(r+1);
                       rank 0's is the N = 1 cloud), the 1+6S-double all-reduce
                       every step — the path partitions into independent point
-                      ranges joined by that one collective. For W > 1 the strong
-                      figure is measured in the same run and reported beside it
-                      (`strong`): ONE 2^20-point cloud split into W spatial
-                      shards — contiguous ranges of the whole cloud's Hilbert
+                      ranges joined by that one collective. For W > 1 --full
+                      measures the strong figure in the same run and reports it
+                      beside it (`strong`): ONE 2^20-point cloud split into W
+                      spatial shards — contiguous ranges of the whole cloud's Hilbert
                       order (fsdf_set_points_range), rebalanced after the settle
                       to equal measured chunk time — with the per-frame ingest
                       both ways (`config.ingest_per_frame`)
@@ -31,29 +38,30 @@ Sharding (contiguous point ranges, uploaded once per frame):
   --points P          weak scaling only: every rank owns its own P-point cloud
   --global-points G   strong scaling only, of a G-point cloud
   --config c4         BASELINE config 4: IRB140, ONE 10·2^20-point cloud, strong
-                      scaling (`value`), the weak figure beside it (`weak`)
-For W > 1 the per-pass all-reduce is also timed on its own (`allreduce_ms`:
+                      scaling (`value`), with --full the weak figure beside it (`weak`)
+For W > 1 --full also times the per-pass all-reduce on its own (`allreduce_ms`:
 host-synchronised all-reduces of the accumulator, mean over `steps`), and the
 backend that ran is named (`config.backend`).
 
 Rank 0 prints one JSON line (contract in the task description) with:
   roofline      the pass kernel on the HBM roofline: algorithmic bytes per launch
                 (24 B in + 36 B out per point) / its mean HIP-event
-                time vs 8 TB/s; `traffic` = PMC bytes per launch of the committed
-                profile (profiles/latest_pmc.json); `valu_issue_frac` = executed
+                time (--full: of a serial re-run of the K passes; otherwise of
+                the timed region) vs 8 TB/s; `traffic` = PMC bytes per launch of
+                the committed profile (profiles/latest_pmc.json); `valu_issue_frac` = executed
                 VALU wave-instructions (PMC) x 2 cycles / (1,024 SIMDs x 2.4 GHz x
                 kernel time); the brute-force-equivalent F_alg rate is under
                 `valu_effective` (it counts work the culling never executes)
-  cpu_baseline  the C oracle on a bounded sample of the same cloud, on this
-                host's cores: culled (sphere lower bounds, exact) as `value`,
+  cpu_baseline  (--full) the C oracle on a bounded sample of the same cloud, on
+                this host's cores: culled (sphere lower bounds, exact) as `value`,
                 brute force (the reference's loop) beside it
-  config        set-points (copy + Hilbert sort) per frame, a measured track!
-                frame (pinned host cloud -> set_points -> fsdf_descend, 30
+  config        the workload; with --full also set-points (copy + Hilbert sort)
+                per frame, a measured track! frame (pinned host cloud -> set_points -> fsdf_descend, 30
                 iterations of estimate_state's default solver; device and host
                 solver loops) and the full CostFunctor iteration (host FK + pass +
                 accumulator read-back + chain rule), measured in the same run
-  telemetry     the GPU's clocks, power and temperatures (sysfs / hipDeviceProp)
-                at the start and end of the timed region
+  telemetry     (--full) the GPU's clocks, power and temperatures (sysfs /
+                hipDeviceProp) at the start and end of the timed region
 """
 from __future__ import annotations
 
@@ -138,7 +146,47 @@ def parse():
                    help="W > 1 strong scaling: contiguous slices of the caller's (shuffled) order instead of ranges "
                         "of the whole cloud's Hilbert order (the round-4 partition; A/B)")
     p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: the serial re-run of the passes (the roofline's "
+                        "kernel time), set-points per frame, the dependent step, passes in flight, the full "
+                        "iteration and the measured track! frame, the CPU baseline, device telemetry and, for "
+                        "W > 1, the all-reduce, the ingest and the other scaling figure. Without it the run "
+                        "sets up, warms up, times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0): "
+                        "accum (the 1+6S-double accumulator, float64) and, per point in the caller's order, kstar "
+                        "(float32), d (float64) and grad (float64 [n,3]); above 64 MB in all a fixed seeded sample "
+                        "of the points, their caller indices in index (float64)")
     return p.parse_args()
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together
+DUMP = None  # run_cloud's copy of the last timed step's outputs (--dump-outputs; the first run_cloud, rank 0)
+
+
+def write_outputs(dirpath, arrs, seed):
+    """--dump-outputs: the last timed step's outputs as DIR/<name>.npy. Per-point
+    arrays go out in the caller's order whatever order the pass wrote them in
+    (resident order: sorted by fsdf_get_permutation's caller index), so that two
+    builds compare point for point; a cloud whose rows exceed DUMP_MAX_BYTES is
+    sampled at fixed seeded rows of that order."""
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "accum.npy"), arrs["accum"].astype(np.float64))
+    if "d" not in arrs:  # (--no-per-point)
+        return
+    perm = arrs.get("perm")
+    n = len(arrs["d"])
+    rows = np.arange(n) if perm is None else np.argsort(perm, kind="stable")
+    index = np.arange(n) if perm is None else perm[rows]
+    row_bytes = 4 + 8 + 24 + 8  # kstar f32, d f64, grad 3 f64, index f64
+    cap = (DUMP_MAX_BYTES - arrs["accum"].size * 8 - 5 * 128) // row_bytes  # (128 B: an .npy header)
+    if n > cap:
+        pick = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, cap, replace=False))
+        rows, index = rows[pick], index[pick]
+        np.save(os.path.join(dirpath, "index.npy"), index.astype(np.float64))
+    np.save(os.path.join(dirpath, "kstar.npy"), arrs["kstar"][rows].astype(np.float32))
+    np.save(os.path.join(dirpath, "d.npy"), arrs["d"][rows].astype(np.float64))
+    np.save(os.path.join(dirpath, "grad.npy"), arrs["grad"][rows].astype(np.float64))
 
 
 def cpu_baseline(manip, pts, q_eval, target_s):
@@ -379,8 +427,8 @@ def main():
     # C4 (ONE 10*2^20 cloud over the GPUs) is strong by definition, the weak
     # figure beside it
     explicit = args.points is not None or args.global_points is not None
-    also_weak = world > 1 and not explicit and scaling == "strong"
-    also_strong = world > 1 and not explicit and scaling == "weak"
+    also_weak = args.full and world > 1 and not explicit and scaling == "strong"
+    also_strong = args.full and world > 1 and not explicit and scaling == "weak"
     manip = getattr(Models, model_name)()
     q_true, q_eval = synthetic.perturbed_configuration(manip, args.seed)
 
@@ -412,7 +460,7 @@ def main():
     poses = [flash.hull_poses(manip, q_eval), flash.hull_poses(manip, q_alt)]
 
     C = max(1, args.inflight)
-    SIDE = args.inflight_side if (world == 1 and args.inflight_side > 1) else 0
+    SIDE = args.inflight_side if (args.full and world == 1 and args.inflight_side > 1) else 0
     CS = max(C, SIDE)  # contexts: the timed region uses the first C, the in-flight side figure the first SIDE
     ctxs = [manip.engine(device=local, precision=args.precision, cull=not args.no_cull,
                          sort_points=not args.no_sort, slot=c) for c in range(CS)]
@@ -461,7 +509,8 @@ def main():
         for cx in ctxs:  # (every context, the side figure's too)
             upload(cx)  # first upload (allocations)
         set_ms = []
-        for _ in range(3):  # once per frame: copy (+ Hilbert sort), every context of the timed region
+        # --full: once per frame, copy (+ Hilbert sort), every context of the timed region
+        for _ in range(3 if args.full else 0):
             t_set = time.perf_counter()
             for cx in ctxs[:C]:
                 upload(cx)
@@ -592,21 +641,22 @@ def main():
                 torch.cuda.synchronize()
             REGROUP_MS = regroup_all()
         del d_pts
-        # K passes one at a time on context 0 (no collective), right after the
-        # settle: the kernel's own launch duration (the roofline's, as rocprofv3
+        # --full: K passes one at a time on context 0 (no collective), right after
+        # the settle: the kernel's own launch duration (the roofline's, as rocprofv3
         # sees it in tools/rocprof_round.sh) and one step's latency
         torch.cuda.synchronize()
-        ctx.profile_pass(True)
-        t_s = time.perf_counter()
-        for i in range(args.steps):
-            ctx.eval_device(poses[i & 1], accums[0][i & 1].data_ptr(), *outs[0])
-        torch.cuda.synchronize()
-        serial_step = (time.perf_counter() - t_s) / args.steps * 1e3
-        k_, p_, l_ = ctx.pass_times()
-        ctx.profile_pass(False)
         global SERIAL
-        SERIAL = {"step_ms": serial_step, "kernel_ms": k_ / max(l_, 1), "pass_and_reduce_ms": p_ / max(l_, 1)}
-        torch.cuda.synchronize()
+        if args.full:
+            ctx.profile_pass(True)
+            t_s = time.perf_counter()
+            for i in range(args.steps):
+                ctx.eval_device(poses[i & 1], accums[0][i & 1].data_ptr(), *outs[0])
+            torch.cuda.synchronize()
+            serial_step = (time.perf_counter() - t_s) / args.steps * 1e3
+            k_, p_, l_ = ctx.pass_times()
+            ctx.profile_pass(False)
+            SERIAL = {"step_ms": serial_step, "kernel_ms": k_ / max(l_, 1), "pass_and_reduce_ms": p_ / max(l_, 1)}
+            torch.cuda.synchronize()
         for i in range(args.warmup):
             step(i)
         drain()
@@ -614,7 +664,7 @@ def main():
         for cx in ctxs:
             cx.profile_pass(True)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        first_run = not TELEMETRY
+        first_run = args.full and not TELEMETRY
         if first_run:
             TELEMETRY["timed_start"] = device_telemetry(local)
         if world > 1:
@@ -641,13 +691,25 @@ def main():
             kernel_ms, pass_ms, launches = kernel_ms + k_, pass_ms + p_, launches + l_
             cx.profile_pass(False)
         elapsed_ = max(wall, ev0.elapsed_time(ev1) / 1e3)
+        # --dump-outputs: the last timed step's accumulator and per-point outputs,
+        # copied before any side figure runs over the same buffers
+        global DUMP
+        if args.dump_outputs and rank == 0 and DUMP is None:
+            i = args.steps - 1
+            c, r_ = i % C, (i // C) % RING
+            DUMP = {"accum": accums[c][r_].cpu().numpy()}
+            if not args.no_per_point:
+                k_, d_, g_ = (x[:ctxs[c].n].cpu().numpy() for x in bufs[c])
+                DUMP.update(kstar=k_, d=d_, grad=g_)
+                if not args.caller_order:
+                    DUMP["perm"] = ctxs[c].permutation()
         # N = 1 side figures, after the timed region: (a) a dependent step — the
         # pass, then the accumulator read back to pinned host memory and the host
         # waits, every step (what a track! iteration pays besides its host FK and
         # chain rule); (b) SIDE independent passes in flight (aggregate throughput)
         global SIDE_RES
         SIDE_RES = {"host_enqueue_ms_per_step": t_enq / args.steps * 1e3}
-        if world == 1:
+        if args.full and world == 1:
             for i in range(3):
                 ctx.eval_device(poses[i & 1], accums[0][i & 1].data_ptr(), *outs[0])
                 h_acc.copy_(accums[0][i & 1], non_blocking=True)
@@ -676,7 +738,7 @@ def main():
                     for s_ in (0, 1):
                         assert torch.equal(accums[c][s_], accums[0][s_]), "in-flight contexts disagree"
         t = torch.tensor([elapsed_, pass_ms / max(launches, 1), kernel_ms / max(launches, 1),
-                          float(np.median(set_ms))], dtype=torch.float64, device=dev)
+                          float(np.median(set_ms)) if set_ms else -1.0], dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         # sanity: the last pass is finite and non-trivial; every context's
@@ -687,20 +749,24 @@ def main():
             for c in range(1, C):
                 for s_ in (0, 1):
                     assert torch.equal(accums[c][s_], accums[0][s_]), "in-flight contexts disagree"
-        return float(t[0]), float(t[1]), float(t[2]), float(t[3])
+        return float(t[0]), float(t[1]), float(t[2]), (float(t[3]) if set_ms else None)
 
     elapsed, timed_pass_ms, timed_kernel_ms, set_points_ms = run_cloud(pts, bounds)
     n = ctx.n  # this rank's resident points
     serial = dict(SERIAL)
     side = dict(SIDE_RES)
-    # the roofline prices the kernel alone on the device (its serial launches,
-    # measured above with HIP events on its stream); with passes in flight each
-    # launch shares the device with its neighbour and lasts longer
-    kernel_avg_ms, pass_avg_ms = serial["kernel_ms"], serial["pass_and_reduce_ms"]
+    # the roofline prices the kernel alone on the device (--full: its serial
+    # launches, measured above with HIP events on its stream); with passes in
+    # flight each launch shares the device with its neighbour and lasts longer.
+    # A plain run has the timed region's launches only (the same at --inflight 1)
+    if args.full:
+        kernel_avg_ms, pass_avg_ms = serial["kernel_ms"], serial["pass_and_reduce_ms"]
+    else:
+        kernel_avg_ms, pass_avg_ms = timed_kernel_ms, timed_pass_ms
 
     allreduce_ms = None
     dependent_ms = side.get("dependent_step_ms")
-    if world > 1:
+    if args.full and world > 1:
         # a dependent iteration (track!: x_{k+1} needs the all-reduced accumulator
         # of x_k): pass, collective, host read-back, every step — the latency the
         # overlap above cannot hide
@@ -772,7 +838,7 @@ def main():
         del whole
         return rec
 
-    ingest = measure_ingest(pts) if world > 1 and bounds is not None else None
+    ingest = measure_ingest(pts) if args.full and world > 1 and bounds is not None else None
 
     weak = None
     if also_weak:
@@ -803,12 +869,14 @@ def main():
             ingest = measure_ingest(pts_s)
 
     iter_ms = frame_rec = None
-    if rank == 0 and world == 1 and not args.no_full_iteration:
+    if rank == 0 and world == 1 and args.full and not args.no_full_iteration:
         ctx.set_stream(None)
         ctx.set_output_order(False)
         iter_ms = full_iteration_ms(manip, ctx, q_eval)
         frame_rec = measured_frame(manip, ctx, pts, q_eval, torch)
 
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, DUMP, args.seed)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = global_points * args.steps / elapsed
@@ -848,6 +916,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "settle_ms": args.settle_ms,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": scaling,
@@ -889,7 +958,7 @@ def main():
                                                  "the timed region; only independent configurations can overlap, a "
                                                  "dependent track! iteration cannot"}
                                         if "inflight_ms_per_pass" in side else None),
-                "serial_step_ms": serial["step_ms"],
+                "serial_step_ms": serial.get("step_ms"),
                 "host_enqueue_ms_per_step": side.get("host_enqueue_ms_per_step"),
                 "serial_step_note": "K passes one at a time on one context, untimed, before the timed region (no "
                                     "collective, per-point outputs written): one pass's latency",
@@ -920,7 +989,9 @@ def main():
                 "kernel": ran, "kernel_ms": kernel_avg_ms,
                 "kernel_ms_source": ("HIP events on the kernel's stream, K passes one at a time between the settle "
                                      "and the timed region (the kernel alone on the device, as in the committed "
-                                     "rocprofv3 summary)"),
+                                     "rocprofv3 summary)" if args.full else
+                                     "HIP events on the kernel's stream inside the timed region (--full: a serial "
+                                     "re-run of the passes, the kernel alone on the device)"),
                 # the pass kernel's mean HIP-event time inside the timed region (= kernel_ms
                 # when passes run one at a time; longer with passes in flight)
                 "kernel_ms_timed_region": timed_kernel_ms,
@@ -938,12 +1009,13 @@ def main():
                                "note": "brute-force F_alg (every plane of every hull, SURVEY.md §8d) per launch / "
                                        "kernel time; culling skips most of it, so the ratio exceeds 1"},
         }
-        out["telemetry"] = TELEMETRY
+        if args.full:
+            out["telemetry"] = TELEMETRY
         if weak is not None:
             out["weak"] = weak
         if strong is not None:
             out["strong"] = strong
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(manip, pts, q_eval, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if RCCL is not None:

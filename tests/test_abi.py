@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT, rng
+from conftest import GOLDEN, ROOT, rng
 
 HEADER = os.path.join(ROOT, "include", "flashsdf.h")
 
@@ -130,12 +130,12 @@ def test_hull_degenerate_inputs():
     assert e.value.status == 1
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout absent (GPU box)")
 def test_stl_ingest_matches_fixture():
-    """read_stl_vertices on the reference STLs reproduces the committed fixture."""
+    """read_stl_vertices on the reference STLs (copies under
+    tests/golden/IRB140/) reproduces the committed fixture."""
     from flash.geometry import read_stl_vertices
     from flash.models import _irb140_fixture
     fx = _irb140_fixture()
-    base = os.path.join(REFERENCE, "examples/data/IRB140/urdf/meshes")
+    base = os.path.join(GOLDEN, "IRB140/urdf/meshes")
     for name, v in fx["meshes"].items():
         assert np.array_equal(read_stl_vertices(os.path.join(base, name)), np.asarray(v))

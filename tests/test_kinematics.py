@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, REFERENCE, rng
+from conftest import GOLDEN, rng
 
 
 def test_irb140_matches_independent_fk(oracle_mod):
@@ -75,11 +75,12 @@ def test_squishable_points_on_scaled_ellipse():
         assert (p[nz] ** 2 / radii[nz] ** 2).sum() == pytest.approx(1.0, rel=1e-12)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout absent (GPU box)")
 def test_load_urdf_equals_fixture_model():
+    """load_urdf on the reference's convex-hull URDF and STLs (copies under
+    tests/golden/IRB140/) builds the committed fixture model."""
     import flash
     from flash import Models
-    u = Models.load_urdf(os.path.join(REFERENCE, "examples/data/IRB140/urdf/irb_140_convhull.urdf"))
+    u = Models.load_urdf(os.path.join(GOLDEN, "IRB140/urdf/irb_140_convhull.urdf"))
     f = Models.irb140()
     q = rng(1).uniform(-1, 1, 6)
     assert np.array_equal(flash.hull_poses(u, q), flash.hull_poses(f, q))

@@ -9,8 +9,8 @@
 #   pytest:FILES    pytest of the given test files only (commas between files)  -> pytest.log
 #   ktrace:ARGS     rocprofv3 --kernel-trace --stats of bench.py ARGS (commas = spaces) -> ktrace_N/ + summary
 #   smoke           __graft_entry__.smoke() (no build: the in-tree .so files travel)  -> smoke.log
-#   bench           bench.py default line            -> bench_default.json
-#   bench:ARGS      bench.py with ARGS (commas = spaces), e.g. bench:--points,131072
+#   bench           bench.py --full default line     -> bench_default.json
+#   bench:ARGS      bench.py --full with ARGS (commas = spaces), e.g. bench:--points,131072
 #   prof            tools/rocprof_round.sh (kernel trace + PMC passes)
 #   ab:LIBS         interleaved A/B of ab/lib_*.so builds (commas between libs)
 #   abn:P:LIBS      bit-for-bit check + A/B at a P-point cloud
@@ -22,7 +22,7 @@
 #   pmclib:LIBS:CTRS  one PMC pass per library build (commas between libs, '+' between counters)
 #   sweep           bench.py at 2^16 .. 2^20 points           -> size_sweep.jsonl
 #   configs         tools/bench_configs.py (BASELINE configs C2-C5, M64)
-#   rehearse        bench.py N=2 on one GPU (gloo, both ranks on device 0)
+#   rehearse        bench.py --full N=2 on one GPU (gloo, both ranks on device 0)
 #   shards          strong-scaling shards stepped alone at W = 1/2/4/8 (tools/spatial_shards.py) -> spatial_shards.jsonl
 #   hsweep:MODEL:SIZES[:EXTRA]  partition tiers / planned pass against cloud size (tools/hpart_sweep.py; MODEL
 #                   irb140 | arm_grid, SIZES and EXTRA arguments comma-separated) -> hpart_sweep_MODEL*.jsonl
@@ -65,12 +65,12 @@ for r in csv.DictReader(open(f)):
         || { echo SMOKE FAILED; tail $O/smoke.log; exit 1; }
       tail -2 $O/smoke.log ;;
     bench)
-      timeout -k 10 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err \
+      timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err \
         || { echo BENCH FAILED; tail $O/bench_default.err; exit 1; }
       cut -c1-400 $O/bench_default.json ;;
     bench:*)
       A=${step#bench:}; A=${A//,/ }; N=$(echo "$A" | tr -c 'a-zA-Z0-9' '_')
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline $A > $O/bench_$N.json 2> $O/bench_$N.err \
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $A > $O/bench_$N.json 2> $O/bench_$N.err \
         || { echo BENCH FAILED; tail $O/bench_$N.err; exit 1; }
       cut -c1-400 $O/bench_$N.json ;;
     prof)
@@ -150,7 +150,7 @@ for r in csv.DictReader(open(f)):
     rehearse)
       export FSDF_BENCH_BACKEND=gloo FSDF_BENCH_DEVICE=0
       timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29611 bench.py --gpus 2 --steps 10 --warmup 2 > $O/rehearse_n2.json 2> $O/rehearse_n2.err \
+        --master-port 29611 bench.py --full --gpus 2 --steps 10 --warmup 2 > $O/rehearse_n2.json 2> $O/rehearse_n2.err \
         || { tail -30 $O/rehearse_n2.err; exit 1; }
       cut -c1-600 $O/rehearse_n2.json
       unset FSDF_BENCH_BACKEND FSDF_BENCH_DEVICE ;;
@@ -194,7 +194,7 @@ for l in open('$O/hpart_sweep_$N.jsonl'):
           || { echo AB NOREGROUP FAILED; tail $D/noregroup_$rep.err; exit 1; }
         for f in head r04 noregroup; do python3 -c "
 import json; d = json.load(open('$D/${f}_$rep.json')); c = d['config']; r = d['roofline']
-print('$f $rep', round(d['value'] / 1e9, 3), 'G', round(d['ms_per_step'], 5), 'serial', round(c['serial_step_ms'], 5),
+print('$f $rep', round(d['value'] / 1e9, 3), 'G', round(d['ms_per_step'], 5), 'serial', c['serial_step_ms'],
       'kernel', round(r['kernel_ms'], 5), 'frac', round(r['frac'], 4))"; done
       done
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
