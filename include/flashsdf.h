@@ -219,7 +219,18 @@ int fsdf_descend(fsdf_ctx* ctx, double* x, int32_t iteration_limit, double rate,
  * skin, no deformation) iterate on the device where the mechanism fits the
  * solver step's 64 KB of LDS, others on the host; 0: always the host loop
  * around fsdf_value_and_gradient, one synchronization per iteration; 2: the
- * device loop is required (FSDF_ERR_STATE otherwise). The device loop enqueues
+ * device loop is required (FSDF_ERR_STATE otherwise; scenes with RBF skins or
+ * deformations are refused); 3: as 1, and scenes with RBF skins or deformations
+ * iterate on the device too — the step then also runs the adjoint of the
+ * skins' weight solve, the deformation gradient and regularizer, and after its
+ * FK the new centres, the (n+4)x(n+4) LU and the weight solve, and writes the
+ * next pass's RBF rows (csrc/rbf_impl.h, the host's arithmetic) — where every
+ * skin's system fits the step's LDS with the rest (n + 4 <= 128 and all LU
+ * factors in the 64 KB), others on the host; 4: as 2 with those scenes
+ * admitted (3 and 4 decide by the same condition: what 4 refuses is what 3
+ * runs on the host). A singular RBF system fails the frame with FSDF_ERR_DEGENERATE, as
+ * on the host. After a device frame of such a scene the RBF rows on the device
+ * are those of the last posed x. The device loop enqueues
  * the frame's passes and solver steps up front and reads x, value and count
  * back once (csrc/solver.hip: FK, chain rule, the clipped NaiveSolver step and
  * the next pass's pose after each pass, the host loop's arithmetic in the same

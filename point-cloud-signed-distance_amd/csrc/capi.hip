@@ -229,7 +229,8 @@ struct fsdf_ctx {
   // arrays (built on the first device descend after fsdf_set_mechanism) and
   // one frame's state; pinned staging for x / divisors in and x, f, flags out
   int solver_device = 1;             // fsdf_set_solver: 1 device where possible (default), 0 host loop,
-                                     // 2 device required
+                                     // 2 device required; 3 / 4: as 1 / 2 with RBF
+                                     // and deformable scenes admitted
   bool solver_tree_ok = false;
   fsdf::SolverTree stree;
   double* d_stree_d = nullptr;       // the tree blob (fsdf::SolverTree::blob)
@@ -1798,6 +1799,7 @@ extern "C" int fsdf_set_rbf_centres(fsdf_ctx* c, int32_t surface, int32_t n_sp, 
   D.piv.resize(n + 4);
   D.G.resize(3 * n);
   D.work.resize(n + 4);
+  c->solver_tree_ok = false;  // (the device loop's tree holds the centres)
   return FSDF_OK;
 }
 
@@ -1806,6 +1808,7 @@ extern "C" int fsdf_set_deformations(fsdf_ctx* c, int32_t n_deform, double weigh
   if (n_deform < 0 || !std::isfinite(weight)) return fail(c, FSDF_ERR_ARG, "set_deformations: bad arguments");
   c->mech.n_deform = n_deform;
   c->mech.weight = weight;
+  c->solver_tree_ok = false;  // (the device loop's state length)
   return FSDF_OK;
 }
 
@@ -2063,10 +2066,23 @@ static int build_solver_tree(fsdf_ctx* c) {
       if (M.surface_body[k] == p) slist.push_back(k);
     soff.push_back((int32_t)slist.size());
   }
+  // RBF skins (declared ones; fsdf_descend takes the device loop only with all of them declared)
+  std::vector<int32_t> rn, rcoff(1, 0), rluoff(1, 0), rbody, rdrow;
+  std::vector<double> rlocal, rvalues;
+  for (const auto& D : M.rbf) {
+    rn.push_back(D.n);
+    rcoff.push_back(rcoff.back() + D.n);
+    rluoff.push_back(rluoff.back() + (D.n + 4) * (D.n + 4));
+    rbody.insert(rbody.end(), D.body.begin(), D.body.end());
+    rdrow.insert(rdrow.end(), D.drow.begin(), D.drow.end());
+    rlocal.insert(rlocal.end(), D.local.begin(), D.local.end());
+    rvalues.insert(rvalues.end(), D.values.begin(), D.values.end());
+  }
   const size_t o_parent = put(M.parent), o_kind = put(M.kind), o_qoff = put(M.qoff), o_dord = put(dord),
                o_doff = put(doff), o_hord = put(hord), o_hoff = put(hoff), o_coff = put(coff), o_clist = put(clist),
                o_soff = put(soff), o_slist = put(slist), o_sb = put(M.surface_body), o_dlist = put(dlist),
-               o_dof = put(dof);
+               o_dof = put(dof), o_rn = put(rn), o_rcoff = put(rcoff), o_rluoff = put(rluoff), o_rbody = put(rbody),
+               o_rdrow = put(rdrow);
   std::vector<double> dv;
   auto putd = [&](const std::vector<double>& v) {
     const size_t at = dv.size();
@@ -2074,7 +2090,7 @@ static int build_solver_tree(fsdf_ctx* c) {
     return at;
   };
   const size_t o_axis = putd(M.axis), o_AR = putd(M.AR), o_At = putd(M.At), o_BR = putd(M.BR), o_Bt = putd(M.Bt),
-               o_FR = putd(M.frame_R), o_Ft = putd(M.frame_t);
+               o_FR = putd(M.frame_R), o_Ft = putd(M.frame_t), o_rlocal = putd(rlocal), o_rvalues = putd(rvalues);
   HIPCHECK(c, hipStreamSynchronize(c->stream));  // (a previous frame's steps may still read the old arrays)
   dfree(c->d_stree_d);
   const size_t bytes = dv.size() * sizeof(double) + iv.size() * sizeof(int32_t);
@@ -2086,8 +2102,22 @@ static int build_solver_tree(fsdf_ctx* c) {
   HIPCHECK(c, hipMemcpy(c->d_stree_d, blob.data(), blob.size(), hipMemcpyHostToDevice));
   fsdf::SolverTree& T = c->stree;
   T.nb = nb;
-  T.nx = M.nq;
+  T.nx = M.nq + 3 * M.n_deform;
+  T.nq = M.nq;
   T.S = S;
+  T.R = (int)rn.size();
+  T.n_deform = M.n_deform;
+  T.rc = rcoff.back();
+  T.rm = T.rc + 4 * T.R;
+  T.rlu = rluoff.back();
+  T.racc = 4 * T.rc + 4 * T.R;
+  T.rbf_n = (int)o_rn;
+  T.rbf_coff = (int)o_rcoff;
+  T.rbf_luoff = (int)o_rluoff;
+  T.rbf_body = (int)o_rbody;
+  T.rbf_drow = (int)o_rdrow;
+  T.rbf_local = (int)o_rlocal;
+  T.rbf_values = (int)o_rvalues;
   T.D = D;
   T.H = H;
   T.blob = c->d_stree_d;
@@ -2129,14 +2159,17 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
                           double tolerance, const double* divisors, double n_points, double* value_out,
                           int32_t* iterations_out) {
   auto& M = c->mech;
-  const int nx = M.nq, nb = M.nb;
+  const int nx = M.nq + 3 * M.n_deform, nb = M.nb;  // (the state: joint coordinates, then the deformations)
   HIPCHECK(c, hipSetDevice(c->device));
   if (!c->solver_tree_ok) {
     const int rc = build_solver_tree(c);
     if (rc) return rc;
   }
-  // device: x [2][nx] (slots by iteration parity) | div [nx] | Rb|tb [2][12 nb] | f; flags [4] int
-  const size_t need = (size_t)3 * nx + 24 * (size_t)nb + 1;
+  // device: x [2][nx] (slots by iteration parity) | div [nx] | Rb|tb [2][12 nb] | f | RBF scenes: the
+  // weight solve's state [2][9 nb + 3 rc + rm + rlu] and row permutation [2][rm] ints; flags [4] int
+  const fsdf::SolverTree& T = c->stree;
+  const size_t rbf_slot = T.R > 0 ? 9 * (size_t)nb + 3 * (size_t)T.rc + (size_t)T.rm + (size_t)T.rlu : 0;
+  const size_t need = (size_t)3 * nx + 24 * (size_t)nb + 1 + 2 * rbf_slot + (T.R > 0 ? (size_t)T.rm + 1 : 0);
   if (c->solver_cap < need) {
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     dfree(c->d_solver);
@@ -2165,6 +2198,10 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
   st.div = divisors ? c->d_solver + 2 * nx : nullptr;
   st.Rb = c->d_solver + 3 * nx;
   st.f = st.Rb + 24 * nb;
+  if (T.R > 0) {
+    st.rbf = st.f + 1;
+    st.prow = (int32_t*)(st.rbf + 2 * rbf_slot);
+  }
   st.flags = c->d_solver_flags;
   st.rate = rate;
   st.max_step = max_step;
@@ -2177,6 +2214,15 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
   // passes below launch no pose kernel; FSDF_POSE_OVERLAP is off, c->pm is
   // the one posed model)
   HIPCHECK(c, fsdf::launch_solver_init(c->stree, st, c->lm, c->pm, c->precision, c->stream));
+  // (the init wrote the first pass's RBF rows; as it was again on every return but a frame's good end)
+  struct RbfReady {
+    fsdf_ctx* c;
+    bool was, keep;
+    ~RbfReady() {
+      if (!keep) c->rbf_ready = was;
+    }
+  } rbf_rows{c, c->rbf_ready, false};
+  if (T.R > 0) c->rbf_ready = true;
   HOST_STAMP(0);
   for (int it = 0; it < iteration_limit; ++it) {
     int rc = run_pass(c, nullptr, c->d_pts, c->n, c->d_accum, nullptr, nullptr, nullptr, nullptr, true, true,
@@ -2211,6 +2257,9 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
 #endif
   memcpy(x, h + (size_t)(flags[1] & 1) * nx, (size_t)nx * sizeof(double));  // (the last iteration's slot)
   if (iterations_out) *iterations_out = flags[1];
+  // (the steps wrote the passes' RBF rows themselves: those of the last posed x are on the device)
+  rbf_rows.keep = !flags[2];
+  if (flags[2] == 3) return fail(c, FSDF_ERR_DEGENERATE, "value_and_gradient: singular RBF system");
   if (flags[2] == 2) return fail(c, FSDF_ERR_ARG, "descend: poses not finite (configuration diverged)");
   if (flags[2]) return fail(c, FSDF_ERR_ARG, "descend: forward kinematics / chain rule (bad configuration)");
   if (value_out) *value_out = h[3 * nx];
@@ -2219,7 +2268,7 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
 
 extern "C" int fsdf_set_solver(fsdf_ctx* c, int32_t device_loop) {
   if (!c) return FSDF_ERR_ARG;
-  if (device_loop < 0 || device_loop > 2) return fail(c, FSDF_ERR_ARG, "set_solver: mode %d", device_loop);
+  if (device_loop < 0 || device_loop > 4) return fail(c, FSDF_ERR_ARG, "set_solver: mode %d", device_loop);
   c->solver_device = device_loop;
   return FSDF_OK;
 }
@@ -2237,19 +2286,35 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
     return fail(c, FSDF_ERR_STATE, "descend: mechanism registered for another surface list (call fsdf_set_mechanism)");
   // rigid scenes (no RBF skin, no deformation) iterate on the device when the
   // mechanism's tree and the step's work arrays fit the step's LDS (M64's 65
-  // bodies: ~45 KB)
+  // bodies: ~45 KB); scenes with RBF skins or deformations too in modes 3 / 4
+  // (fsdf_set_solver), their skins' LU factors and work arrays counted. A
+  // scene whose skins are not all declared, or name a deformation row that
+  // does not exist, takes the host loop, which reports it.
   // (the step poses c->pm itself: not with the double-buffered pose overlap)
-  bool device_loop = c->solver_device && iteration_limit > 0 && c->lm.R == 0 && Mc.n_deform == 0 && c->n > 0 &&
-                     !FSDF_POSE_OVERLAP;
+  const bool rigid = c->lm.R == 0 && Mc.n_deform == 0;
+  const bool required = c->solver_device == 2 || c->solver_device == 4;
+  bool declared = (int)Mc.rbf.size() == c->lm.R || c->lm.R == 0;
+  for (const auto& D : Mc.rbf) {
+    declared = declared && D.n > 0;
+    for (int j = 0; j < D.n; ++j) declared = declared && D.drow[j] < Mc.n_deform;
+  }
+  bool device_loop = c->solver_device && iteration_limit > 0 && (rigid || (c->solver_device >= 3 && declared)) &&
+                     c->n > 0 && !FSDF_POSE_OVERLAP;
   if (device_loop && !c->solver_tree_ok) {
     HIPCHECK(c, hipSetDevice(c->device));
     const int rc = build_solver_tree(c);
     if (rc) return rc;
   }
-  device_loop = device_loop && fsdf::solver_fits(Mc.nb, Mc.nq, c->lm.S, c->stree.ni);
-  if (c->solver_device == 2 && iteration_limit > 0 && !device_loop)
-    return fail(c, FSDF_ERR_STATE, "descend: the device loop was required (fsdf_set_solver 2) but the scene %s",
-                c->lm.R > 0 || Mc.n_deform > 0 ? "has RBF skins / deformations" :
+  if (device_loop) {
+    std::vector<int32_t> rbf_n;
+    for (const auto& D : Mc.rbf) rbf_n.push_back(D.n);
+    device_loop = fsdf::solver_fits(Mc.nb, Mc.nq + 3 * Mc.n_deform, c->lm.S, c->stree.ni, c->stree.nd, Mc.n_deform,
+                                    (int)rbf_n.size(), rbf_n.data());
+  }
+  if (required && iteration_limit > 0 && !device_loop && (rigid || c->solver_device == 2 || declared))
+    return fail(c, FSDF_ERR_STATE, "descend: the device loop was required (fsdf_set_solver %d) but the scene %s",
+                c->solver_device,
+                c->solver_device == 2 && !rigid ? "has RBF skins / deformations" :
                 c->n == 0 ? "has no resident points" : "does not fit the solver step's LDS");
   if (device_loop)
     return descend_device(c, x, iteration_limit, rate, max_step, tolerance, divisors, n_points, value_out,

@@ -267,7 +267,8 @@ hipError_t regroup_points(void** d_pts, int64_t* pts_cap, int64_t n, int precisi
 // chain rule. The solver kernels copy both buffers into LDS first, so every
 // later access in their level loops is an LDS access.
 struct SolverTree {
-  int nb = 0, nx = 0, S = 0;
+  int nb = 0, nx = 0, S = 0;  // nx = nq + 3 n_deform: the whole state (x, g, divisors)
+  int nq = 0;                 // joint coordinates (the deformations δ follow them in x)
   int D = 0;  // depth of the deepest body
   int H = 0;  // height levels of bodies with children: height_order[height_off[h] .. ) at height h+1
   int narrow = 0;  // every height level has <= 10 parents: the subtree sums run in one wave
@@ -285,6 +286,16 @@ struct SolverTree {
   int chain_list = 0, chain_off = 0;  // (chains) [nb+1]: body b, its child, grandchild, ...
   // offsets into the doubles
   int axis = 0, AR = 0, At = 0, BR = 0, Bt = 0, frame_R = 0, frame_t = 0;  // frames: [S][9], [S][3]
+  // RBF skins (fsdf_set_rbf_centres, in surface order) and deformations: R
+  // skins of n_r centres (m_r = n_r + 4), rc = Σ n_r, rm = Σ m_r, rlu = Σ m_r²,
+  // racc = Σ (4 n_r + 4) (the accumulator block after the 1 + 6S). Skin r's
+  // centres start at rbf_coff[r], its m-vectors at rbf_coff[r] + 4r, its rows
+  // at rbf_coff[r] + r, its accumulator block at 4 rbf_coff[r] + 4r, its LU at
+  // rbf_luoff[r].
+  int R = 0, n_deform = 0, rc = 0, rm = 0, rlu = 0, racc = 0;
+  int rbf_n = 0, rbf_coff = 0, rbf_luoff = 0;  // ints [R], [R+1], [R+1]
+  int rbf_body = 0, rbf_drow = 0;              // ints [rc]: the centre's body (-1: world) / deformation row (-1: none)
+  int rbf_local = 0, rbf_values = 0;           // doubles [rc][3], [rc]
 };
 // One frame's solver state (device), two slots by iteration parity (a step
 // launch's workgroups read slot (k & 1) while its workgroup 0 writes slot
@@ -292,18 +303,27 @@ struct SolverTree {
 // (Rb [nb][9] then tb [nb][3] per slot); optional divisors [nx]; f = the last
 // evaluation's cost / n_points; flags [3] = (done — the skip flag of the
 // frame's launches —, iterations (x of the last one in slot iterations & 1),
-// error: 1 FK / chain rule, 2 a non-finite pose). (The next pass's posed
+// error: 1 FK / chain rule, 2 a non-finite pose, 3 a singular RBF system). (The next pass's posed
 // model is written by the step itself: pose_impl.h.)
 struct SolverState {
   double* x = nullptr;
   const double* div = nullptr;
   double *Rb = nullptr, *f = nullptr;
   int* flags = nullptr;
+  // RBF / deformable scenes: what the next step's adjoint needs of this
+  // step's FK and weight solve, two slots as x: rbf [2][9 nb + 3 rc + rm + rlu]
+  // = the bodies' R | the centres | u | the LU factors (rows in pivoted
+  // order, as the host's in-place factorization leaves them); prow [2][rm] the
+  // row permutation (pivoted row i is row prow[i] of the system)
+  double* rbf = nullptr;
+  int32_t* prow = nullptr;
   double rate = 0.0, max_step = 0.0, tol = 0.0, n_points = 1.0, weight = 0.0;
   int limit = 0;
 };
-// the step's LDS (the tree, the accumulator and the work arrays) fits one workgroup
-bool solver_fits(int nb, int nx, int S, int ni);
+// the step's LDS (the tree, the accumulator and the work arrays, the kernels'
+// static __shared__ included) fits one workgroup. nx = nq + 3 n_deform; ni, nd:
+// the tree blob's ints and doubles; rbf_n [R]: the skins' centre counts
+bool solver_fits(int nb, int nx, int S, int ni, int nd, int n_deform, int R, const int32_t* rbf_n);
 // diagnostic builds (-DFSDF_SOLVER_TIMES=1): the last step's phase clocks (16, 100 MHz)
 void solver_times(unsigned long long* out);
 // FK of st.x -> Rb, tb and the first pass's posed model pm (flags zeroed by the

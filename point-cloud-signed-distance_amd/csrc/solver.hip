@@ -1,5 +1,5 @@
-// solver.hip — estimate_state's solver iteration on the device, for rigid
-// (hull-only) scenes: after a residual pass and its reduce, one launch turns
+// solver.hip — estimate_state's solver iteration on the device: after a
+// residual pass and its reduce, one launch turns
 // the accumulator into the next configuration, the next surface poses and the
 // next pass's posed model, so a whole frame of iterations is enqueued with no
 // host round trip (fsdf_descend, capi.hip descend_device; the default for
@@ -23,6 +23,19 @@
 // values) and then poses its 1,024 of the model's pose items (pose_impl.h);
 // workgroup 0 alone writes the state, double-buffered by iteration parity.
 //
+// Scenes with RBF skins or deformations (fsdf_set_solver 3 / 4; the EXT
+// kernels) add the host loop's halves around the pass, from rbf_impl.h:
+//   before the chain rule  per skin μ = M⁻¹λ from the pass's RBF accumulator
+//               block with the LU of the solve that produced the pass's rows,
+//               G_j (sum over i ascending), body wrenches in centre order,
+//               ∂c/∂δ = Rᵀ G + 2 weight δ, cost + weight Σδ² (capi.hip
+//               iteration_finish); x, g, the divisors are [nq + 3 n_deform]
+//   after the FK  centres c_j = R_b (p_j + δ_j) + t_b, the fill, PA = LU, the
+//               weight solve, the next pass's RBF rows in the context
+//               precision (capi.hip iteration_prepare); centres, u, LU and
+//               the row permutation go to the state slot for the next step
+// A singular / non-finite system ends the frame with error 3.
+//
 // The pass / reduce / step launches of later iterations read `flags[0]`
 // (SolverState::flags) and return at once after convergence; the remaining
 // iterations of the frame cost their (empty) launches only.
@@ -31,6 +44,7 @@
 #include "fsdf_internal.h"
 #include "kin_impl.h"
 #include "pose_impl.h"
+#include "rbf_impl.h"
 
 #ifndef FSDF_SOLVER_TIMES
 #define FSDF_SOLVER_TIMES 0  // diagnostic builds: per-phase clocks of the step (capi.hip prints them)
@@ -63,16 +77,30 @@ __device__ unsigned long long g_solver_times[64];
 // P [12S] (the surface poses the pose items read).
 // Every array the level loops touch is here: a level costs LDS latency and a
 // barrier, not a global-memory round trip.
+// RBF / deformable scenes (EXT kernels) append: cen [3 rc] | u [rm] | lu [rlu]
+// (the last solve's centres, weights and LU factors, staged for the adjoint,
+// then this step's) | mu [rm] | G [3 rc] | bw [6 nb] (the RBF chain's body
+// wrenches) | prow [rm] ints (the LU's row permutation); the accumulator is
+// [1 + 6S + racc] and R is staged too (the last FK's, for ∂c/∂δ).
 struct Lds {
   const double *axis, *AR, *At, *BR, *Bt, *FR, *Ft;
   double *acc, *Rb, *tb, *sub, *LR, *Lt, *R, *t, *x, *g, *div, *P;
   const int32_t *parent, *kind, *qoff, *plist, *poff, *hord, *hoff, *coff, *clist, *soff, *slist, *sbody;
   const int32_t *chlist, *choff;
+  const double *rlocal, *rvalues;
+  const int32_t *rn, *rcoff, *rluoff, *rbody, *rdrow;
+  double *cen, *u, *lu, *mu, *G, *bw;
+  int32_t* prow;
 };
 
 // the doubles after the blob: acc | Rb | tb | x | div | sub | LR | Lt | R | t | g | P (the surface poses)
 __host__ __device__ inline size_t work_doubles(int nb, int nx, int S) {
   return 1 + 18 * (size_t)S + 42 * (size_t)nb + 3 * (size_t)nx;
+}
+// and of an RBF / deformable scene: the accumulator's RBF block (after the
+// 1 + 6S, so counted here) and the arrays above
+__host__ __device__ inline size_t ext_doubles(int nb, int rc, int rm, int rlu, int racc) {
+  return (size_t)racc + 6 * (size_t)rc + 2 * (size_t)rm + (size_t)rlu + 6 * (size_t)nb + ((size_t)rm + 1) / 2;
 }
 
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
@@ -91,7 +119,7 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 constexpr int kBlobPer = 12;  // 16-B blob chunks per thread: blobs up to 48 KB
 constexpr int kDynPer = 8;    // dynamic doubles per thread (accum, Rb|tb, x, div): up to 2,048
 
-template <int NT>
+template <int NT, bool EXT>
 __device__ Lds stage(const SolverTree& T, const SolverState& st, double* lds, const double* accum, int slot) {
   // (per-thread load counts for NT threads: the same totals as kBlobPer / kDynPer at kSolverBlock)
   constexpr int BP = (kBlobPer * kSolverBlock + NT - 1) / NT, DP = (kDynPer * kSolverBlock + NT - 1) / NT;
@@ -105,7 +133,8 @@ __device__ Lds stage(const SolverTree& T, const SolverState& st, double* lds, co
     const int i = tid + u * NT;
     bv[u] = i < T.chunks16 ? blob[i] : D2{0.0, 0.0};
   }
-  const int na = accum ? 1 + 6 * S : 0, nr = accum ? 12 * nb : 0, nd_ = st.div ? nx : 0;
+  const int nacc = 1 + 6 * S + (EXT ? T.racc : 0);  // (EXT: the RBF block follows the surface wrenches)
+  const int na = accum ? nacc : 0, nr = accum ? 12 * nb : 0, nd_ = st.div ? nx : 0;
   const int ndyn = na + nr + nx + nd_;
   double dv[DP];
 #pragma unroll
@@ -150,7 +179,7 @@ __device__ Lds stage(const SolverTree& T, const SolverState& st, double* lds, co
   L.choff = iv + T.chain_off;
   d += 2 * T.chunks16;  // (the blob, padded to 16 B)
   L.acc = d;
-  d += 1 + 6 * S;
+  d += nacc;
   L.Rb = d;
   d += 9 * nb;
   L.tb = d;
@@ -172,6 +201,31 @@ __device__ Lds stage(const SolverTree& T, const SolverState& st, double* lds, co
   L.g = d;
   d += nx;
   L.P = d;
+  if (EXT) {
+    const double* bd = lds;
+    const int32_t* bi = (const int32_t*)(bd + T.nd);
+    L.rlocal = bd + T.rbf_local;
+    L.rvalues = bd + T.rbf_values;
+    L.rn = bi + T.rbf_n;
+    L.rcoff = bi + T.rbf_coff;
+    L.rluoff = bi + T.rbf_luoff;
+    L.rbody = bi + T.rbf_body;
+    L.rdrow = bi + T.rbf_drow;
+    d += 12 * S;
+    L.cen = d;
+    d += 3 * T.rc;
+    L.u = d;
+    d += T.rm;
+    L.lu = d;
+    d += T.rlu;
+    L.mu = d;
+    d += T.rm;
+    L.G = d;
+    d += 3 * T.rc;
+    L.bw = d;
+    d += 6 * nb;
+    L.prow = (int32_t*)d;
+  }
   // the dynamic doubles land at acc (accum | Rb tb | x | div are contiguous
   // there too; without an accumulator x lands at L.x)
 #pragma unroll
@@ -182,6 +236,309 @@ __device__ Lds stage(const SolverTree& T, const SolverState& st, double* lds, co
   }
   for (int i = tid; i < nx; i += NT) L.g[i] = 0.0;
   return L;
+}
+
+// ---- RBF skins: the weight solve and its adjoint (rbf_impl.h) ------------------
+// The last step's R | centres | u | LU (the state slot the step reads) into
+// L.R and L.cen | L.u | L.lu (contiguous), and the row permutation: every
+// thread's loads before its first store, as stage(). (8 doubles per thread:
+// 64 KB, more than a carve that fits holds; solver_fits checks it, and that
+// the row maps of all skins together, rm ints, are one load per thread.)
+constexpr int kRbfPer = 8;
+
+template <int NT>
+__device__ void stage_rbf(const SolverTree& T, const SolverState& st, const Lds& L, int slot) {
+  const int tid = threadIdx.x, nR = 9 * T.nb, tot = nR + 3 * T.rc + T.rm + T.rlu;
+  const double* src = st.rbf + (size_t)slot * tot;
+  double v[kRbfPer];
+#pragma unroll
+  for (int u = 0; u < kRbfPer; ++u) {
+    const int i = tid + u * NT;
+    v[u] = i < tot ? src[i] : 0.0;
+  }
+  const int pr = tid < T.rm ? st.prow[(size_t)slot * T.rm + tid] : 0;  // (rm <= NT: solver_fits)
+#pragma unroll
+  for (int u = 0; u < kRbfPer; ++u) {
+    const int i = tid + u * NT;
+    if (i < nR) L.R[i] = v[u];
+    else if (i < tot) L.cen[i - nR] = v[u];
+  }
+  if (tid < T.rm) L.prow[tid] = pr;
+}
+
+// the LU's row map, rows 0..63 in `lo` and 64..127 in `hi` of the wave's lanes (i uniform)
+__device__ __forceinline__ int prow_get(int lo, int hi, int i) {
+  return i < 64 ? __builtin_amdgcn_readlane(lo, i) : __builtin_amdgcn_readlane(hi, i - 64);
+}
+
+// v moved across the lanes of each row of 16 by a DPP control (both halves)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, 0xf, 0xf, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+// the wave's largest v (no NaN among them; all 64 lanes active): rotations by
+// 1, 2, 4, 8 within each row of 16 lanes (row_ror), then the four rows' maxima
+// from their first lanes. A maximum is exact in any order.
+__device__ __forceinline__ double wave_max_f64(double v) {
+  v = fmax(v, dpp_f64<0x121>(v));
+  v = fmax(v, dpp_f64<0x122>(v));
+  v = fmax(v, dpp_f64<0x124>(v));
+  v = fmax(v, dpp_f64<0x128>(v));
+  return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+}
+
+// PA = LU of the m x m system A (LDS, m <= 128) by the workgroup: the host's
+// lu_factor (rbf_impl.h) with the rows left where they are and the row map
+// swapped instead (logical row i = stored row prow[i]; lane i of every wave
+// holds prow[i] and prow[i + 64], the same in every wave). Step k: a barrier,
+// then every working wave finds the pivot — lane i reads a_ik of its rows,
+// the wave's maximum |.|, the first lane that holds it: the first index of the
+// largest |.| under the host's strict > (rbf::lu_pivot), a NaN below row k
+// never taken and a NaN in row k, a zero or an infinite maximum singular —
+// and row i > k is eliminated by one wave, a lane per column right of k.
+// Column k is read by every wave's pivot search, so no wave writes it in step
+// k: the multipliers l_ik (from the a_ik the pivot search read, the host's
+// product) wait in wave 0's registers and go into column k after the next
+// step's barrier, when column k is no longer read by any step. With that, one
+// barrier per step orders every LDS access: step k writes columns > k of rows
+// > k (each entry by one lane) and column k - 1, and reads column k, the pivot
+// row (not written) and the entries its own lane writes. Eliminations of a
+// step are independent of each other: the host's bits.
+// A singular / non-finite column sets *sing and goes on with p = k (in
+// bounds; the frame fails). Ends with prow (LDS) written, no barrier after.
+template <int NT>
+__device__ void rbf_factor(int m, double* A, int32_t* prow, int* sing) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int W = m - 1 < NT / 64 ? (m > 1 ? m - 1 : 1) : NT / 64;  // (a wave per row below the first pivot)
+  const bool two = m > 64;
+  const int j0 = lane, j1 = lane + 64;  // (this lane's rows in the pivot search, its columns in the elimination)
+  const bool in0 = j0 < m, in1 = j1 < m;
+  int plo = lane, phi = lane + 64;
+  double l0 = 0.0, l1 = 0.0;  // (wave 0: the last step's multipliers of this lane's rows, and where they go)
+  int at0 = -1, at1 = -1;
+  for (int k = 0; k < m; ++k) {
+    __syncthreads();
+    if (wave >= W) continue;
+    if (wave == 0) {  // (column k - 1: read by no step from here on)
+      if (at0 >= 0) A[at0] = l0;
+      if (at1 >= 0) A[at1] = l1;
+    }
+    const int e0 = plo * m + k, e1 = phi * m + k;  // (before the swap: the stored rows this lane read)
+    const bool r0 = in0 && j0 >= k, r1 = two && in1 && j1 >= k;
+    const double s0 = r0 ? A[e0] : 0.0, s1 = r1 ? A[e1] : 0.0;
+    double v0 = r0 ? fabs(s0) : -1.0, v1 = r1 ? fabs(s1) : -1.0;
+    const bool n0 = v0 != v0, n1 = v1 != v1;
+    const bool nan_k = __builtin_amdgcn_ballot_w64((n0 && j0 == k) || (n1 && j1 == k)) != 0;
+    if (n0) v0 = -1.0;
+    if (n1) v1 = -1.0;
+    const double best = wave_max_f64(fmax(v0, v1));
+    const uint64_t b0 = __builtin_amdgcn_ballot_w64(v0 == best);
+    int p = b0 ? __builtin_ctzll(b0) : 64 + __builtin_ctzll(__builtin_amdgcn_ballot_w64(v1 == best) | (1ull << 63));
+    if (nan_k || !(best > 0.0) || !isfinite(best)) {
+      *sing = 1;  // (every writer writes the same value)
+      p = k;
+    }
+    if (p != k) {
+      const int a = prow_get(plo, phi, k), b = prow_get(plo, phi, p);
+      if (lane == (k & 63)) {
+        if (k < 64) plo = b;
+        else phi = b;
+      }
+      if (lane == (p & 63)) {
+        if (p < 64) plo = a;
+        else phi = a;
+      }
+    }
+    const double* Ak = A + prow_get(plo, phi, k) * m;
+    const bool c0 = in0 && j0 > k, c1 = two && in1 && j1 > k;  // (columns right of the pivot)
+    const double ak0 = c0 ? Ak[j0] : 0.0, ak1 = c1 ? Ak[j1] : 0.0;
+    const double inv = 1.0 / Ak[k];
+    if (wave == 0) {  // (every row the search read but the pivot's, the lane that read row p included)
+      l0 = rbf::lu_multiplier(s0, inv);
+      l1 = rbf::lu_multiplier(s1, inv);
+      at0 = r0 && j0 != p ? e0 : -1;
+      at1 = r1 && j1 != p ? e1 : -1;
+    }
+    for (int i = k + 1 + wave; i < m; i += W) {
+      double* Ai = A + prow_get(plo, phi, i) * m;
+      const double aik = Ai[k], a0 = c0 ? Ai[j0] : 0.0, a1 = c1 ? Ai[j1] : 0.0;
+      const double l = rbf::lu_multiplier(aik, inv);
+      if (c0) Ai[j0] = rbf::lu_eliminate(a0, l, ak0);
+      if (c1) Ai[j1] = rbf::lu_eliminate(a1, l, ak1);
+    }
+  }
+  // (the last step has no row below its pivot: nothing waits)
+  __syncthreads();
+  if (wave == 0) {
+    if (in0) prow[j0] = plo;
+    if (in1) prow[j1] = phi;
+  }
+}
+
+// One wave solves A x = b from the factors: lane i (and i + 64) owns row i.
+// rhs(r): entry r of the system's right-hand side (row i's is rhs(prow[i]):
+// the host's swaps of b); stored: the factors lie in stored rows (this step's,
+// rbf_factor) or in pivoted order (the staged ones). Forward: s_i -= l_ij b_j
+// for j ascending, b_j from lane j once it is final — every row's terms in the
+// host's order. Backward: row i's products u_ij b_j in the lanes j > i, then
+// subtracted from b_i in ascending j (the host's order starts at j = i + 1,
+// the last b to become known: the sum cannot start earlier), read straight
+// from the lanes. x into out [m] (LDS); *sing = 1 if an entry is not finite.
+template <class Rhs>
+__device__ void rbf_wave_solve(int m, const double* lu, const int32_t* prow, bool stored, Rhs rhs, double* out,
+                               int* sing) {
+  const int lane = threadIdx.x & 63, i0 = lane, i1 = lane + 64;
+  const bool a0 = i0 < m, a1 = i1 < m;
+  const int r0 = a0 ? prow[i0] : 0, r1 = a1 ? prow[i1] : 0;
+  double s0 = a0 ? rhs(r0) : 0.0, s1 = a1 ? rhs(r1) : 0.0;
+  const double* row0 = lu + (stored ? r0 : (a0 ? i0 : 0)) * m;
+  const double* row1 = lu + (stored ? r1 : (a1 ? i1 : 0)) * m;
+  // (the next column's factors load while this one's terms are subtracted)
+  const bool two = m > 64;
+  double n0 = row0[0], n1 = two ? row1[0] : 0.0;
+  for (int j = 0; j < m - 1; ++j) {
+    const double l0 = n0, l1 = n1;
+    if (j + 2 < m) {
+      n0 = row0[j + 1];
+      if (two) n1 = row1[j + 1];
+    }
+    const double bj = j < 64 ? readlane_f64(s0, j) : readlane_f64(s1, j - 64);
+    if (a0 && i0 > j) s0 = rbf::subst_term(s0, l0, bj);
+    if (a1 && i1 > j) s1 = rbf::subst_term(s1, l1, bj);
+  }
+  for (int i = m - 1; i >= 0; --i) {
+    const int ri = stored ? prow_get(r0, r1, i) : i;
+    const double* rowi = lu + ri * m;
+    const double p0 = a0 && i0 > i ? rowi[i0] * s0 : 0.0;  // (subst_term's product; its subtraction below)
+    const double p1 = a1 && i1 > i ? rowi[i1] * s1 : 0.0;
+    const double dii = rowi[i];
+    double s = i < 64 ? readlane_f64(s0, i) : readlane_f64(s1, i - 64);
+    const int e0 = m < 64 ? m : 64;
+    for (int j = i + 1; j < e0; ++j) s = s - readlane_f64(p0, j);
+    for (int j = i + 1 > 64 ? i + 1 : 64; j < m; ++j) s = s - readlane_f64(p1, j - 64);
+    s = s / dii;
+    if (lane == (i & 63)) {
+      if (i < 64) s0 = s;
+      else s1 = s;
+    }
+  }
+  if (a0) out[i0] = s0;
+  if (a1) out[i1] = s1;
+  if (sing && ((a0 && !isfinite(s0)) || (a1 && !isfinite(s1)))) *sing = 1;
+}
+
+// After the step's FK (L.R, L.t, L.x): the centres c_j = R_b (p_j + δ_j) + t_b
+// (capi.hip iteration_prepare's expression), every skin's fill, LU and weight
+// solve: L.cen, L.lu (stored rows), L.prow, L.u. Ends with a barrier.
+template <int NT>
+__device__ void rbf_prepare(const SolverTree& T, const Lds& L, int* sing) {
+  const int tid = threadIdx.x, wave = tid >> 6;
+  for (int e = tid; e < 3 * T.rc; e += NT) {
+    const int j = e / 3, i = e - 3 * j, b = L.rbody[j], dr = L.rdrow[j];
+    double p0 = L.rlocal[3 * j], p1 = L.rlocal[3 * j + 1], p2 = L.rlocal[3 * j + 2];
+    if (dr >= 0) {
+      const double* dl = L.x + T.nq + 3 * dr;
+      p0 += dl[0];
+      p1 += dl[1];
+      p2 += dl[2];
+    }
+    const double pi = i == 0 ? p0 : (i == 1 ? p1 : p2);
+    L.cen[e] = b < 0 ? pi
+                     : (L.R[9 * b + 3 * i] * p0 + L.R[9 * b + 3 * i + 1] * p1 + L.R[9 * b + 3 * i + 2] * p2) +
+                           L.t[3 * b + i];
+  }
+  __syncthreads();
+  for (int r = 0; r < T.R; ++r) {
+    const int n = L.rn[r], m = n + 4;
+    double* A = L.lu + L.rluoff[r];
+    const double* c = L.cen + 3 * L.rcoff[r];
+    for (int e = tid; e < m * m; e += NT) A[e] = rbf::matrix_entry(n, c, e / m, e % m);
+  }
+  for (int r = 0; r < T.R; ++r)  // (each begins with a barrier)
+    rbf_factor<NT>(L.rn[r] + 4, L.lu + L.rluoff[r], L.prow + L.rcoff[r] + 4 * r, sing);
+  __syncthreads();
+  for (int r = wave; r < T.R; r += NT / 64) {
+    const int n = L.rn[r], mo = L.rcoff[r] + 4 * r;
+    const double* val = L.rvalues + L.rcoff[r];
+    rbf_wave_solve(n + 4, L.lu + L.rluoff[r], L.prow + mo, true,
+                   [&](int i) { return rbf::rhs_entry(n, val, i); }, L.u + mo, sing);
+  }
+  __syncthreads();
+}
+
+// Before the chain rule: the adjoint of the last weight solve from the pass's
+// RBF accumulator block (capi.hip iteration_finish): per skin μ = M⁻¹λ (a
+// wave), the pair factors 3 |c_j - c_i| (into the LU's place, done with), G_j
+// (a thread per (centre, component), i ascending), then the body wrenches in
+// centre order, skins in surface order (a thread per (body, component)) into
+// L.bw, ∂c/∂δ = Rᵀ G (+ the regularizer's 2 weight δ: the host adds it last)
+// into L.g, and Σ δ² in index order into *reg. Ends with a barrier.
+template <int NT>
+__device__ void rbf_adjoint(const SolverTree& T, const SolverState& st, const Lds& L, double* reg) {
+  const int tid = threadIdx.x, wave = tid >> 6, nb = T.nb, R = T.R, rc = T.rc;
+  const double* block = L.acc + 1 + 6 * T.S;
+  for (int r = wave; r < R; r += NT / 64) {
+    const int mo = L.rcoff[r] + 4 * r;
+    const double* lam = block + 4 * L.rcoff[r] + 4 * r;
+    rbf_wave_solve(L.rn[r] + 4, L.lu + L.rluoff[r], L.prow + mo, false, [&](int i) { return lam[i]; }, L.mu + mo,
+                   nullptr);
+  }
+  __syncthreads();
+  for (int r = 0; r < R; ++r) {
+    const int n = L.rn[r];
+    double* r3 = L.lu + L.rluoff[r];
+    const double* c = L.cen + 3 * L.rcoff[r];
+    for (int e = tid; e < n * n; e += NT) r3[e] = rbf::adjoint_r3(c, e / n, e % n);
+  }
+  __syncthreads();
+  for (int e = tid; e < 3 * rc; e += NT) {
+    const int jj = e / 3, c = e - 3 * jj;
+    int r = 0;
+    while (jj >= L.rcoff[r + 1]) ++r;
+    const int n = L.rn[r], co = L.rcoff[r], mo = co + 4 * r, j = jj - co;
+    const double* E = block + 4 * co + 4 * r + (n + 4);
+    L.G[e] = rbf::adjoint_entry(n, L.cen + 3 * co, L.u + mo, L.mu + mo, E, j, c, L.lu + L.rluoff[r] + j * n);
+  }
+  __syncthreads();
+  const int nd3 = 3 * T.n_deform;
+  for (int e = tid; e < 6 * nb + nd3; e += NT) {
+    if (e < 6 * nb) {
+      const int b = e / 6, q = e - 6 * b;
+      double w = 0.0;
+      for (int jj = 0; jj < rc; ++jj) {
+        if (L.rbody[jj] != b) continue;
+        const double* G = L.G + 3 * jj;
+        const double* cj = L.cen + 3 * jj;
+        const double v = q < 3   ? G[q]
+                         : q == 3 ? cj[1] * G[2] - cj[2] * G[1]
+                         : q == 4 ? cj[2] * G[0] - cj[0] * G[2]
+                                  : cj[0] * G[1] - cj[1] * G[0];
+        w -= v;
+      }
+      L.bw[e] = w;
+    } else {
+      const int k = e - 6 * nb, row = k / 3, i = k - 3 * row;
+      double gd = 0.0;
+      for (int jj = 0; jj < rc; ++jj) {
+        if (L.rdrow[jj] != row) continue;
+        const double* G = L.G + 3 * jj;
+        const int b = L.rbody[jj];
+        gd += b < 0 ? G[i] : (L.R[9 * b + i] * G[0] + L.R[9 * b + 3 + i] * G[1] + L.R[9 * b + 6 + i] * G[2]);
+      }
+      const double dl = L.x[T.nq + k];
+      gd += 2.0 * st.weight * dl;
+      L.g[T.nq + k] = gd;
+    }
+  }
+  if (tid == NT - 1) {
+    double s = 0.0;
+    for (int i = 0; i < nd3; ++i) s += L.x[T.nq + i] * L.x[T.nq + i];
+    *reg = s;
+  }
+  __syncthreads();
 }
 
 // FK of L.x into L.R, t, Rb, tb (LDS; *bad |= 1 for a zero quaternion /
@@ -274,9 +631,13 @@ __device__ void fk(const SolverTree& T, const Lds& L, int* bad, int it0 = -1) {
 // iteration count and the done / error flags. Every global store is issued
 // after the last barrier (a barrier's release fence would wait for them).
 // pose = false: the last iteration (no pass follows) publishes x and the flags only.
-template <typename TP, int NT>
+// EXT with skins: the next pass's RBF rows too (centre, w_j per centre, then
+// a, b; the context precision: (float) of the f64 rows, as launch_to_f32), and
+// what the next step's adjoint needs (SolverState::rbf, prow); sing: a
+// singular weight solve (error 3, as the host fails before it poses).
+template <typename TP, int NT, bool EXT>
 __device__ void publish(const SolverTree& T, const SolverState& st, const Lds& L, bool pose, int bad, double f,
-                        int it, int done, const LocalModel& lm, const PosedModel& pm) {
+                        int it, int done, const LocalModel& lm, const PosedModel& pm, int sing = 0) {
   const int tid = threadIdx.x, nb = T.nb, wg = blockIdx.x;
   const int slot = it & 1;  // (the state the next step reads: x, Rb, tb of iteration it)
   __shared__ int nonfinite;
@@ -304,12 +665,37 @@ __device__ void publish(const SolverTree& T, const SolverState& st, const Lds& L
     for (int i = tid; i < 9 * nb; i += NT) Rb[i] = L.Rb[i];
     for (int i = tid; i < 3 * nb; i += NT) Rb[9 * nb + i] = L.tb[i];
   }
+  if (EXT && pose && T.R > 0) {
+    TP* rows = (TP*)pm.rbf_rows;
+    const int nR = 9 * nb;
+    double* dst = st.rbf + (size_t)slot * (nR + 3 * T.rc + T.rm + T.rlu);
+    for (int i = tid; i < nR; i += NT) dst[i] = L.R[i];
+    dst += nR;
+    for (int i = tid; i < 3 * T.rc + T.rm; i += NT) dst[i] = L.cen[i];  // (cen | u adjacent)
+    dst += 3 * T.rc + T.rm;
+    for (int r = 0; r < T.R; ++r) {
+      const int n = L.rn[r], m = n + 4, co = L.rcoff[r], mo = co + 4 * r;
+      const double *c = L.cen + 3 * co, *u = L.u + mo, *A = L.lu + L.rluoff[r];
+      const int32_t* pr = L.prow + mo;
+      for (int e = tid; e < 4 * (n + 1); e += NT) {
+        const int j = e >> 2, q = e & 3;
+        const double v = j < n ? (q < 3 ? c[3 * j + q] : u[j]) : u[n + q];
+        rows[4 * (size_t)(co + r) + e] = (TP)v;
+      }
+      // the factors in pivoted order, as the host's in-place swaps leave them
+      for (int e = tid; e < m * m; e += NT) dst[L.rluoff[r] + e] = A[pr[e / m] * m + e % m];
+      for (int i = tid; i < m; i += NT) st.prow[(size_t)slot * T.rm + mo + i] = pr[i];
+    }
+  }
   if (it > 0)  // (the init's x is slot 0's own, which its workgroups are reading)
     for (int i = tid; i < T.nx; i += NT) st.x[(size_t)slot * T.nx + i] = L.x[i];
   if (tid == 0) {
     *st.f = f;
     st.flags[1] = it;
-    if (pose && nonfinite) {
+    if (EXT && sing && !bad) {
+      st.flags[2] = 3;
+      st.flags[0] = 1;
+    } else if (pose && nonfinite) {
       st.flags[2] = 2;
       st.flags[0] = 1;
     } else if (bad || done) {
@@ -319,42 +705,54 @@ __device__ void publish(const SolverTree& T, const SolverState& st, const Lds& L
   }
 }
 
-template <typename TP>
+template <typename TP, bool EXT>
 __global__ __launch_bounds__(kStepThreads) void solver_init_kernel(SolverTree T, SolverState st, LocalModel lm,
                                                                    PosedModel pm) {
   extern __shared__ double lds[];
-  __shared__ int bad;
+  __shared__ int bad, sing;
   const int tid = threadIdx.x;
-  if (tid == 0) bad = 0;
-  const Lds L = stage<kStepThreads>(T, st, lds, nullptr, 0);  // (x0 in slot 0)
+  if (tid == 0) {
+    bad = 0;
+    sing = 0;
+  }
+  const Lds L = stage<kStepThreads, EXT>(T, st, lds, nullptr, 0);  // (x0 in slot 0)
   __syncthreads();
   fk<kStepThreads>(T, L, &bad);  // (ends with a barrier; the host zeroed the flags before this launch)
-  publish<TP, kStepThreads>(T, st, L, true, bad, 0.0, 0, 0, lm, pm);
+  if (EXT && T.R > 0) rbf_prepare<kStepThreads>(T, L, &sing);  // (ends with a barrier)
+  publish<TP, kStepThreads, EXT>(T, st, L, true, bad, 0.0, 0, 0, lm, pm, EXT ? sing : 0);
 }
 
 // One step over NT threads (solver_step_kernel: kStepThreads). (A launch
 // that also did the pass's final reduce — its last workgroup running the step
 // — measured no faster: the hand-off between workgroups costs what the launch
 // saves; branch archive/fused-reduce-step)
-template <typename TP, int NT>
+template <typename TP, int NT, bool EXT>
 __device__ void step_body(const SolverTree& T, const SolverState& st, const double* __restrict__ accum,
                           double* __restrict__ lds, const LocalModel& lm, const PosedModel& pm, int it_before) {
-  // (the frame's done flag loads with the stage's loads; the check waits for it.
-  // Workgroup 0 of this launch may set it at its end: a workgroup that reads it
-  // set returns — no pass follows a converged step)
-  const int done = __builtin_nontemporal_load(st.flags);
-  __shared__ int bad, verdict;
-  __shared__ double s_f;
+  // (the frame's done flag loads with the stage's loads — thread 0's, into LDS:
+  // workgroup 0 of this launch may set the flag at its end, so two threads'
+  // own loads could disagree; after the stage's barrier the whole workgroup
+  // branches on the one value. A workgroup that reads it set returns — no
+  // pass follows a converged step)
+  __shared__ int bad, verdict, s_done, sing;
+  __shared__ double s_f, s_reg;
   const int tid = threadIdx.x, nb = T.nb, nx = T.nx;
+  if (tid == 0) s_done = __builtin_nontemporal_load(st.flags);
 #if FSDF_SOLVER_TIMES
   const int it0 = it_before;
 #endif
   STAMP(0);
-  if (tid == 0) bad = 0;
-  const Lds L = stage<NT>(T, st, lds, accum, it_before & 1);
-  if (done) return;  // converged (or failed): the frame's remaining steps are no-ops (uniform)
+  if (tid == 0) {
+    bad = 0;
+    if (EXT) sing = 0;
+  }
+  const Lds L = stage<NT, EXT>(T, st, lds, accum, it_before & 1);
+  if (EXT && T.R > 0) stage_rbf<NT>(T, st, L, it_before & 1);
   __syncthreads();
+  if (s_done) return;  // converged (or failed): the frame's remaining steps are no-ops (workgroup-uniform)
   STAMP(1);
+  const bool skins = EXT && T.R > 0;
+  if (EXT) rbf_adjoint<NT>(T, st, L, &s_reg);  // (ends with a barrier)
   if (T.chains) {
     // chains (every non-root body has <= 1 child): body b's subtree sum along
     // its chain, deepest first — sub[a] = own[a] + sub[child], own[a] the body's
@@ -367,7 +765,7 @@ __device__ void step_body(const SolverTree& T, const SolverState& st, const doub
     double* own = L.LR;
     for (int i = tid; i < 6 * (nb - 1); i += NT) {
       const int a = 1 + i / 6, j = i % 6;
-      double o = 0.0;
+      double o = skins ? L.bw[6 * a + j] : 0.0;  // (fsdf_config_gradient starts from the RBF chain's body wrench)
       for (int u = L.soff[a]; u < L.soff[a + 1]; ++u) o += L.acc[1 + 6 * L.slist[u] + j];
       own[6 * a + j] = o;
     }
@@ -392,7 +790,7 @@ __device__ void step_body(const SolverTree& T, const SolverState& st, const doub
     // body wrenches: each body's surfaces in index order (fsdf_config_gradient)
     for (int i = tid; i < 6 * nb; i += NT) {
       const int b = i / 6, j = i - 6 * b;
-      double s = 0.0;
+      double s = skins ? L.bw[i] : 0.0;
       for (int q = L.soff[b]; q < L.soff[b + 1]; ++q) s += L.acc[1 + 6 * L.slist[q] + j];
       L.sub[i] = s;
     }
@@ -458,7 +856,7 @@ __device__ void step_body(const SolverTree& T, const SolverState& st, const doub
   }
   const int it = it_before + 1;
   if (tid == 0) {
-    const double cost = L.acc[0] + st.weight * 0.0;  // (rigid: the regularizer's sum is 0.0)
+    const double cost = L.acc[0] + st.weight * (EXT ? s_reg : 0.0);  // (rigid: the regularizer's sum is 0.0)
     s_f = cost / st.n_points;
     verdict = bad ? 3 : (sqrt(nrm2) < st.tol ? 1 : (it >= st.limit ? 2 : 0));
   }
@@ -466,13 +864,13 @@ __device__ void step_body(const SolverTree& T, const SolverState& st, const doub
   const int v = verdict;
   const double f = s_f;
   if (v == 3 || v == 1) {  // failed / converged: x stays
-    publish<TP, NT>(T, st, L, false, v == 3, f, it, 1, lm, pm);
+    publish<TP, NT, EXT>(T, st, L, false, v == 3, f, it, 1, lm, pm);
     return;
   }
   for (int i = tid; i < nx; i += NT) L.x[i] = L.x[i] + kin::clipped_step(st.rate, L.g[i], st.max_step);
   if (v == 2) {  // the last iteration: no pass follows
     __syncthreads();
-    publish<TP, NT>(T, st, L, false, 0, f, it, 1, lm, pm);
+    publish<TP, NT, EXT>(T, st, L, false, 0, f, it, 1, lm, pm);
     return;
   }
   __syncthreads();
@@ -483,31 +881,76 @@ __device__ void step_body(const SolverTree& T, const SolverState& st, const doub
   fk<NT>(T, L, &bad);  // (ends with a barrier)
 #endif
   STAMP(6);
-  publish<TP, NT>(T, st, L, true, bad, f, it, 0, lm, pm);
+  if (skins) rbf_prepare<NT>(T, L, &sing);  // (ends with a barrier)
+  publish<TP, NT, EXT>(T, st, L, true, bad, f, it, 0, lm, pm, EXT ? sing : 0);
   STAMP(9);
 }
 
-template <typename TP>
+template <typename TP, bool EXT>
 __global__ __launch_bounds__(kStepThreads) void solver_step_kernel(SolverTree T, SolverState st,
                                                                    const double* __restrict__ accum, LocalModel lm,
                                                                    PosedModel pm, int it_before) {
   extern __shared__ double lds[];
-  step_body<TP, kStepThreads>(T, st, accum, lds, lm, pm, it_before);
+  step_body<TP, kStepThreads, EXT>(T, st, accum, lds, lm, pm, it_before);
 }
 
+bool extended(const SolverTree& T) { return T.R > 0 || T.n_deform > 0; }
+
 size_t solver_lds_bytes(const SolverTree& T) {
-  return (size_t)T.chunks16 * 16 + work_doubles(T.nb, T.nx, T.S) * sizeof(double);
+  return (size_t)T.chunks16 * 16 +
+         (work_doubles(T.nb, T.nx, T.S) + (extended(T) ? ext_doubles(T.nb, T.rc, T.rm, T.rlu, T.racc) : 0)) *
+             sizeof(double);
+}
+
+// the most static __shared__ any of the solver kernels declares (the flags and
+// sums of step_body / publish), which the 64 KB of a workgroup also hold
+size_t solver_static_lds() {
+  static size_t cached = 0;
+  static bool known = false;
+  if (!known) {
+    const void* fns[] = {(const void*)solver_init_kernel<double, false>, (const void*)solver_init_kernel<float, false>,
+                         (const void*)solver_init_kernel<double, true>,  (const void*)solver_init_kernel<float, true>,
+                         (const void*)solver_step_kernel<double, false>, (const void*)solver_step_kernel<float, false>,
+                         (const void*)solver_step_kernel<double, true>,  (const void*)solver_step_kernel<float, true>};
+    size_t most = 0;
+    for (const void* f : fns) {
+      hipFuncAttributes a;
+      // (a failed query: an allowance above what the kernels declare today)
+      const size_t b = hipFuncGetAttributes(&a, f) == hipSuccess ? a.sharedSizeBytes : 256;
+      most = b > most ? b : most;
+    }
+    cached = most;
+    known = true;
+  }
+  return cached;
 }
 
 }  // namespace
 
-// the blob (27 nb + 12 S doubles + ni ints) within kBlobPer chunks per thread,
-// the dynamic loads within kDynPer, the whole carve within 64 KB of LDS
-bool solver_fits(int nb, int nx, int S, int ni) {
-  const size_t blob = ((27 * (size_t)nb + 12 * (size_t)S) * 8 + (size_t)ni * 4 + 15) / 16;
-  const size_t dyn = 1 + 6 * (size_t)S + 12 * (size_t)nb + 2 * (size_t)nx;
+// the blob (nd doubles + ni ints) within kBlobPer chunks per thread, the
+// dynamic loads (the accumulator with its RBF block, Rb | tb, x, divisors)
+// within kDynPer, every skin's system within the two rows per lane of the
+// solves, the skins' state within stage_rbf's loads, and the whole carve — the LU and work arrays of the skins included —
+// with the kernels' static __shared__ within 64 KB of LDS
+bool solver_fits(int nb, int nx, int S, int ni, int nd, int n_deform, int R, const int32_t* rbf_n) {
+  size_t rc = 0, rm = 0, rlu = 0, racc = 0;
+  for (int r = 0; r < R; ++r) {
+    const size_t n = (size_t)rbf_n[r], m = n + 4;
+    if (m > 128) return false;
+    rc += n;
+    rm += m;
+    rlu += m * m;
+    racc += 4 * n + 4;
+  }
+  const bool ext = R > 0 || n_deform > 0;  // (the EXT kernels' carve)
+  const size_t blob = ((size_t)nd * 8 + (size_t)ni * 4 + 15) / 16;
+  const size_t dyn = 1 + 6 * (size_t)S + racc + 12 * (size_t)nb + 2 * (size_t)nx;
+  const size_t work = work_doubles(nb, nx, S) + (ext ? ext_doubles(nb, (int)rc, (int)rm, (int)rlu, (int)racc) : 0);
+  // (stage_rbf: a slot of the weight solve's state in kRbfPer loads per thread, the row map in one)
+  const bool stage_rbf_fits =
+      9 * (size_t)nb + 3 * rc + rm + rlu <= (size_t)kRbfPer * kStepThreads && rm <= (size_t)kStepThreads;
   return nb >= 1 && blob <= (size_t)kBlobPer * kSolverBlock && dyn <= (size_t)kDynPer * kSolverBlock &&
-         blob * 16 + work_doubles(nb, nx, S) * 8 <= 65536;
+         stage_rbf_fits && blob * 16 + work * 8 + solver_static_lds() <= 65536;
 }
 
 // one workgroup per kStepThreads work items of the pose, each running the whole
@@ -520,12 +963,15 @@ static dim3 solver_grid(const LocalModel& lm) {
 
 hipError_t launch_solver_init(const SolverTree& T, const SolverState& st, const LocalModel& lm,
                               const PosedModel& pm, int precision, hipStream_t s) {
-  if (precision == 64)
-    hipLaunchKernelGGL(solver_init_kernel<double>, solver_grid(lm), dim3(kStepThreads), solver_lds_bytes(T), s, T, st,
-                       lm, pm);
-  else
-    hipLaunchKernelGGL(solver_init_kernel<float>, solver_grid(lm), dim3(kStepThreads), solver_lds_bytes(T), s, T, st,
-                       lm, pm);
+  const dim3 g = solver_grid(lm), b(kStepThreads);
+  const size_t lds = solver_lds_bytes(T);
+  if (extended(T)) {
+    if (precision == 64) hipLaunchKernelGGL((solver_init_kernel<double, true>), g, b, lds, s, T, st, lm, pm);
+    else hipLaunchKernelGGL((solver_init_kernel<float, true>), g, b, lds, s, T, st, lm, pm);
+  } else {
+    if (precision == 64) hipLaunchKernelGGL((solver_init_kernel<double, false>), g, b, lds, s, T, st, lm, pm);
+    else hipLaunchKernelGGL((solver_init_kernel<float, false>), g, b, lds, s, T, st, lm, pm);
+  }
   return hipGetLastError();
 }
 
@@ -540,14 +986,18 @@ void solver_times(unsigned long long* out) {
 hipError_t launch_solver_step(const SolverTree& T, const SolverState& st, const double* d_accum,
                               const LocalModel& lm, const PosedModel& pm, int precision, int it_before,
                               hipStream_t s) {
-  if (precision == 64)
-    hipLaunchKernelGGL(solver_step_kernel<double>, solver_grid(lm), dim3(kStepThreads), solver_lds_bytes(T), s, T, st,
-                       d_accum, lm, pm, it_before);
-  else
-    hipLaunchKernelGGL(solver_step_kernel<float>, solver_grid(lm), dim3(kStepThreads), solver_lds_bytes(T), s, T, st,
-                       d_accum, lm, pm, it_before);
+  const dim3 g = solver_grid(lm), b(kStepThreads);
+  const size_t lds = solver_lds_bytes(T);
+  if (extended(T)) {
+    if (precision == 64)
+      hipLaunchKernelGGL((solver_step_kernel<double, true>), g, b, lds, s, T, st, d_accum, lm, pm, it_before);
+    else hipLaunchKernelGGL((solver_step_kernel<float, true>), g, b, lds, s, T, st, d_accum, lm, pm, it_before);
+  } else {
+    if (precision == 64)
+      hipLaunchKernelGGL((solver_step_kernel<double, false>), g, b, lds, s, T, st, d_accum, lm, pm, it_before);
+    else hipLaunchKernelGGL((solver_step_kernel<float, false>), g, b, lds, s, T, st, d_accum, lm, pm, it_before);
+  }
   return hipGetLastError();
 }
-
 
 }  // namespace fsdf

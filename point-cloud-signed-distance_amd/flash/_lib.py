@@ -314,8 +314,14 @@ class Context:
         """fsdf_set_solver: descend's iterations on the device where the scene
         allows (True / 1, the default: rigid scenes), required there
         ("require" / 2: FSDF_ERR_STATE otherwise), or the host loop around
-        value_and_gradient (False / 0)."""
-        mode = 2 if device_loop == "require" else int(device_loop)
+        value_and_gradient (False / 0). "all" / 3: as True, and scenes with
+        RBF skins or deformations iterate on the device too where their
+        skins' systems fit the step (the host loop otherwise);
+        "require-all" / 4: as "require" with those scenes admitted."""
+        mode = {"require": 2, "all": 3, "require-all": 4}.get(device_loop) if isinstance(device_loop, str) \
+            else int(device_loop)
+        if mode is None:
+            raise ValueError(f"set_solver: unknown mode {device_loop!r}")
         check(self._lib.fsdf_set_solver(self._ctx, mode), self._ctx, "set_solver")
 
     def regroup_points(self):

@@ -14,8 +14,9 @@ path); set_points once (sorted). Then the product's unit of work per config —
 a track! frame through the native solver loop (CostFunctor.descend =
 fsdf_descend: estimate_state's NaiveSolver rate 0.1, max_step 0.5, 30
 iterations, tolerance 0 so every frame runs all 30, src/tracking.jl:12-15) on
-the resident cloud: ms per iteration with the host loop and, for rigid scenes,
-the device loop (csrc/solver.hip), and tracking point-evals/s.
+the resident cloud: ms per iteration with the host loop and with the device
+loop (csrc/solver.hip; "require-all": RBF and deformable scenes too, where
+their systems fit the step), and tracking point-evals/s.
 
     python tools/bench_configs.py [--reps 20] [--json out.json]
 """
@@ -66,19 +67,20 @@ def run(name, m, x, pts, precision, reps):
 def track_frame(m, x, pts, precision, iters=30, frames=3):
     """Median of `frames` native solver frames (after one untimed) on the
     resident cloud: fsdf_descend with the host loop and, where the scene allows
-    it (rigid: no RBF skin, no deformation), the device loop."""
+    it, the device loop ("require-all": rigid scenes, and scenes with RBF skins
+    or deformations whose systems fit the solver step)."""
     import statistics
     from flash.gradientdescent import CostFunctor
     from flash._lib import FlashNativeError
     cf = CostFunctor(m, pts, precision=precision)
     x0 = np.asarray(x, np.float64)
     out = {}
-    for name, mode in (("host_loop", False), ("device_loop", "require")):
+    for name, mode in (("host_loop", False), ("device_loop", "require-all")):
         cf.ctx.set_solver(mode)
         try:
             cf.descend(x0, iters, 0.1, 0.5, 0.0, None, float(len(pts)))
         except FlashNativeError:
-            continue  # (device loop: RBF scenes iterate on the host)
+            continue  # (device loop: the scene does not fit the solver step)
         ts = []
         for _ in range(frames):
             t = time.perf_counter()

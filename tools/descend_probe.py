@@ -8,7 +8,12 @@ iteration's launches (tools/gpu_run.sh step `descend`):
 
 then `python3 tools/descend_probe.py --trace OUT/.../run_kernel_trace.csv` prints per
 kernel the mean duration and, per iteration of the device loop, the span from
-one solver step's end to the next (the iteration's device time incl. gaps)."""
+one solver step's end to the next (the iteration's device time incl. gaps).
+
+`--scene c3|c5|two_link_arm` runs an RBF / deformable scene instead (beanbag,
+m = 11; irb_and_squishable, m = 17; two_link_arm, m = 50; 2^16 points unless
+--points is given), its device loop through fsdf_set_solver 4 ("require-all"):
+the solver step with the skins' LU in it."""
 import argparse
 import csv
 import os
@@ -27,7 +32,7 @@ def run(args):
     from flash import Models, synthetic
     m = Models.arm_grid() if args.model == "m64" else Models.irb140()
     q_true, q_eval = synthetic.perturbed_configuration(m, 1234)
-    pts = synthetic.depth_cloud(m, q_true, args.points, seed=1234 + 17)
+    pts = synthetic.depth_cloud(m, q_true, args.points or 1 << 20, seed=1234 + 17)
     ctx = m.engine(0, 64)
     surf = m.surfaces
     ctx.set_mechanism(m.mechanism, [s.body for s in surf], [s.frame.R for s in surf], [s.frame.t for s in surf])
@@ -41,6 +46,32 @@ def run(args):
             ms.append((time.perf_counter() - t0) * 1e3)
         print(f"{'device' if dev_loop else 'host'} loop: frame {statistics.median(ms):.3f} ms, {its} iterations, "
               f"f {val:.9g}", flush=True)
+
+
+def run_scene(args):
+    import torch  # noqa: F401  (the HIP runtime torch loads, before libflashsdf)
+    import flash
+    from flash import Models, synthetic
+    from flash.gradientdescent import CostFunctor
+    if args.scene == "c5":
+        m, x = Models.irb_and_squishable()
+        x = np.asarray(x, np.float64)
+    else:
+        m = Models.beanbag() if args.scene == "c3" else Models.two_link_arm()
+        x = np.zeros(flash.num_states(m))
+        x[:m.mechanism.num_positions] = m.mechanism.zero_configuration()
+    pts = synthetic.skin_cloud(m, x, args.points or 1 << 16, seed=5)
+    x0 = x + np.random.default_rng(6).normal(0.0, 0.02, len(x))
+    cf = CostFunctor(m, pts)
+    for mode in ("require-all", False):
+        cf.ctx.set_solver(mode)
+        ms = []
+        for _ in range(args.frames + 1):
+            t0 = time.perf_counter()
+            _, val, its = cf.descend(x0, 30, 0.1, 0.5, 0.0, None, float(len(pts)))
+            ms.append((time.perf_counter() - t0) * 1e3)
+        print(f"{args.scene} {'device' if mode else 'host'} loop: frame {statistics.median(ms[1:]):.3f} ms, "
+              f"{its} iterations, {1e3 * statistics.median(ms[1:]) / its:.1f} us / iteration, f {val:.9g}", flush=True)
 
 
 def trace(path):
@@ -96,11 +127,14 @@ def trace(path):
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--model", default="m64", choices=("m64", "irb140"))
-    p.add_argument("--points", type=int, default=1 << 20)
+    p.add_argument("--scene", default=None, choices=("c3", "c5", "two_link_arm"))
+    p.add_argument("--points", type=int, default=None)
     p.add_argument("--frames", type=int, default=5)
     p.add_argument("--trace", default=None)
     a = p.parse_args()
     if a.trace:
         trace(a.trace)
+    elif a.scene:
+        run_scene(a)
     else:
         run(a)
