@@ -240,6 +240,48 @@ int fsdf_descend(fsdf_ctx* ctx, double* x, int32_t iteration_limit, double rate,
  * per fresh 2^20 frame 1.5 % (M64) or level (IRB140). */
 int fsdf_set_solver(fsdf_ctx* ctx, int32_t device_loop);
 
+/* ---- second-order solver: host side (no device) -------------------------------
+ * The cost is a sum of squares, c = Σ_p d*(p)^2, so a Gauss-Newton step with
+ * Levenberg-Marquardt damping fits it (the reference's notebooks swap in a
+ * second-order solver, Ipopt in examples/squishable.ipynb, where the naive one
+ * is too slow). For a point p with nearest surface k and world gradient
+ * n = ∇d*(p), let w_p = (n, p × n) ∈ R^6 — the accumulator's wrench order: force
+ * slots, then the moment about the world origin — and per surface the second
+ * moments
+ *     moments[k][21] = Σ_{p: k*(p)=k} w_p w_pᵀ     (upper triangle, row-major:
+ *                                                    00 01 .. 05 11 .. 55)
+ * The two functions below are the host half of that solver: the matrix JᵀJ
+ * from the moments, and one damped step. The library does not reduce the
+ * moments on the device yet (today they come from the per-point outputs of
+ * fsdf_eval, formed by the caller), so no solver loop of the library uses them.
+ *
+ * fsdf_gauss_newton_matrix, the sibling of fsdf_config_gradient: the
+ * Gauss-Newton matrix A [nq][nq] = Σ_k S_b(k) M_k S_b(k)ᵀ of the mechanism from
+ * the per-surface moments [nsurf][21], where S_b (nq x 6) is the linear map
+ * fsdf_config_gradient applies to a wrench on body b = surface_body[k] (-1:
+ * skipped): ∂d*(p)/∂x_i = (S_b)_i · w_p; 2A is the Gauss-Newton Hessian of the
+ * cost. Its rows are the joints' motion rows of the chain rule, the quaternion
+ * rows with their (I − q̂q̂ᵀ)/|q| projection at the caller's un-normalised q.
+ * Composite form: moments summed per body, then over subtrees, then each
+ * coordinate against those on its path to the root — O(n_dof · depth · 36).
+ * Tree arrays, Rb / tb and q as fsdf_config_gradient; work = 36 nb + 6 nq
+ * doubles. A is symmetric (exactly) and positive semi-definite when the
+ * moments are. flash/mechanism.py gauss_newton_matrix_numpy is the numpy twin. */
+int fsdf_gauss_newton_matrix(int32_t nb, const int32_t* parent, const int32_t* kind, const int32_t* qoff,
+                             const double* axis, const double* Rb, const double* tb, const double* q, int32_t nsurf,
+                             const int32_t* surface_body, const double* moments, int32_t nq, double* work,
+                             double* A_out);
+/* One damped step: D_ii = max(H_ii, 1e-12 max_j H_jj); Cholesky of
+ * H + lambda diag(D) (H symmetric [n][n], its lower triangle is read);
+ * dx_out = clamp(−(H + lambda D)^-1 g, ±max_step) component-wise; work =
+ * n^2 + n doubles. FSDF_ERR_DEGENERATE when the factorisation meets a
+ * non-positive or non-finite pivot (or the solve is not finite).
+ * flash.tracking.LevenbergMarquardt loops over it: a trial that does not lower
+ * the cost is rejected and lambda raised tenfold, an accepted one lowers it
+ * tenfold. */
+int fsdf_lm_step(int32_t n, const double* H, const double* g, double lambda, double max_step, double* work,
+                 double* dx_out);
+
 /* ---- context ---------------------------------------------------------------- */
 int fsdf_create(fsdf_ctx** out, const fsdf_opts* opts);
 int fsdf_destroy(fsdf_ctx* ctx);

@@ -1,0 +1,181 @@
+// gauss_newton.cpp — host side of the second-order tracking solver (no device):
+// the Gauss-Newton matrix of the mechanism from the per-surface second moments
+// of the residual, and one damped (Levenberg-Marquardt) step.
+//
+// For a point p on a surface of body b, ∂d*(p)/∂x_i = s_i · w_p, with w_p =
+// (∇d*, p × ∇d*) and s_i the motion row of joint coordinate i — the row the
+// chain rule (kin_impl.h joint_gradient) contracts a wrench with — when i's
+// joint is b's or an ancestor's, and 0 otherwise. s_i depends on the joint
+// alone, so with M_k = Σ w wᵀ per surface
+//
+//   A = JᵀJ = Σ_k S_b(k) M_k S_b(k)ᵀ,   A_ij = s_iᵀ C_deeper(i, j) s_j
+//
+// where C_b sums M_k over the surfaces of b's subtree and deeper(i, j) is the
+// deeper of the two joints' bodies when one is the other's ancestor (A_ij = 0
+// when neither is): per-body sums, subtree sums (children before parents),
+// then every coordinate against the coordinates on its path to the root.
+
+#include <math.h>
+#include <stdint.h>
+
+#include "flashsdf.h"
+
+namespace {
+
+inline int joint_width(int kind) { return kind == 1 ? 1 : (kind == 2 ? 7 : 0); }
+
+// The motion rows of body b's joint, rows [width][6]: g_i = rows_i · (F, M) is
+// joint_gradient's entry i, the same expressions in the same order (revolute
+// ω = Rb·axis, v = tb × ω, row = −(v, ω); quaternion-floating: the four
+// rotation columns through E(q̂) with the normalization projection 1/|q| at
+// the caller's un-normalised q, then the translation columns −(Rb e_j, 0)).
+bool joint_rows(int kind, const double* a, const double* R, const double* o, const double* q, double* rows) {
+  if (kind == 1) {
+    double w[3], v[3];
+    for (int i = 0; i < 3; ++i) w[i] = R[3 * i] * a[0] + R[3 * i + 1] * a[1] + R[3 * i + 2] * a[2];
+    v[0] = o[1] * w[2] - o[2] * w[1];
+    v[1] = o[2] * w[0] - o[0] * w[2];
+    v[2] = o[0] * w[1] - o[1] * w[0];
+    for (int i = 0; i < 3; ++i) {
+      rows[i] = -v[i];
+      rows[3 + i] = -w[i];
+    }
+    return true;
+  }
+  if (kind != 2) return kind == 0;
+  const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (!(nrm > 0)) return false;
+  const double W = q[0] / nrm, X = q[1] / nrm, Y = q[2] / nrm, Z = q[3] / nrm;
+  const double E[3][4] = {{-X, W, -Z, Y}, {-Y, Z, W, -X}, {-Z, -Y, X, W}};
+  double org[3];  // world origin of the frame after the joint
+  for (int i = 0; i < 3; ++i) org[i] = (R[3 * i] * q[4] + R[3 * i + 1] * q[5] + R[3 * i + 2] * q[6]) + o[i];
+  for (int j = 0; j < 4; ++j) {
+    double w[3], v[3];
+    for (int i = 0; i < 3; ++i)
+      w[i] = R[3 * i] * (2.0 * E[0][j]) + R[3 * i + 1] * (2.0 * E[1][j]) + R[3 * i + 2] * (2.0 * E[2][j]);
+    v[0] = org[1] * w[2] - org[2] * w[1];
+    v[1] = org[2] * w[0] - org[0] * w[2];
+    v[2] = org[0] * w[1] - org[1] * w[0];
+    for (int i = 0; i < 3; ++i) {
+      rows[6 * j + i] = -v[i] / nrm;
+      rows[6 * j + 3 + i] = -w[i] / nrm;
+    }
+  }
+  for (int j = 0; j < 3; ++j) {
+    double* r = rows + 6 * (4 + j);
+    r[0] = -R[j];
+    r[1] = -R[3 + j];
+    r[2] = -R[6 + j];
+    r[3] = r[4] = r[5] = 0.0;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int fsdf_gauss_newton_matrix(int32_t nb, const int32_t* parent, const int32_t* kind, const int32_t* qoff,
+                                        const double* axis, const double* Rb, const double* tb, const double* q,
+                                        int32_t nsurf, const int32_t* surface_body, const double* moments, int32_t nq,
+                                        double* work, double* A_out) {
+  if (nb < 1 || nq < 0 || !parent || !kind || !qoff || !axis || !Rb || !tb || !q || !work || (nq > 0 && !A_out) ||
+      nsurf < 0 || (nsurf > 0 && (!surface_body || !moments)))
+    return FSDF_ERR_ARG;
+  double* C = work;                        // [nb][36] subtree moment sums
+  double* rows = work + (size_t)36 * nb;   // [nq][6] motion rows by coordinate
+  for (size_t i = 0; i < (size_t)36 * nb; ++i) C[i] = 0.0;
+  for (size_t i = 0; i < (size_t)6 * nq; ++i) rows[i] = 0.0;
+  for (size_t i = 0; i < (size_t)nq * nq; ++i) A_out[i] = 0.0;
+  for (int k = 0; k < nsurf; ++k) {
+    const int b = surface_body[k];
+    if (b < 0) continue;
+    if (b >= nb) return FSDF_ERR_ARG;
+    const double* M = moments + 21 * k;
+    double* Cb = C + 36 * b;
+    int e = 0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j, ++e) {
+        Cb[6 * i + j] += M[e];
+        if (j != i) Cb[6 * j + i] += M[e];
+      }
+  }
+  for (int b = nb - 1; b >= 1; --b) {
+    const int p = parent[b];
+    if (p < 0 || p >= b) return FSDF_ERR_ARG;  // topological order required
+    for (int j = 0; j < 36; ++j) C[36 * p + j] += C[36 * b + j];
+  }
+  for (int b = 1; b < nb; ++b) {
+    const int w = joint_width(kind[b]);
+    if (kind[b] < 0 || kind[b] > 2 || (w && (qoff[b] < 0 || qoff[b] + w > nq))) return FSDF_ERR_ARG;
+    if (w && !joint_rows(kind[b], axis + 3 * b, Rb + 9 * b, tb + 3 * b, q + qoff[b], rows + 6 * qoff[b]))
+      return FSDF_ERR_ARG;
+  }
+  for (int b = 1; b < nb; ++b) {
+    const int wb = joint_width(kind[b]);
+    const double* Cb = C + 36 * b;
+    for (int dj = 0; dj < wb; ++dj) {
+      const int cj = qoff[b] + dj;
+      const double* sj = rows + 6 * cj;
+      double u[6];
+      for (int i = 0; i < 6; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < 6; ++j) s += Cb[6 * i + j] * sj[j];
+        u[i] = s;
+      }
+      for (int a = b; a >= 1; a = parent[a]) {
+        const int wa = a == b ? dj + 1 : joint_width(kind[a]);  // own joint: the upper triangle, mirrored
+        for (int di = 0; di < wa; ++di) {
+          const int ci = qoff[a] + di;
+          const double* si = rows + 6 * ci;
+          double s = 0.0;
+          for (int j = 0; j < 6; ++j) s += si[j] * u[j];
+          A_out[(size_t)ci * nq + cj] = s;
+          A_out[(size_t)cj * nq + ci] = s;
+        }
+      }
+    }
+  }
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_lm_step(int32_t n, const double* H, const double* g, double lambda, double max_step, double* work,
+                            double* dx_out) {
+  if (n < 0 || (n > 0 && (!H || !g || !work || !dx_out))) return FSDF_ERR_ARG;
+  double* L = work;                    // [n][n], lower triangle
+  double* y = work + (size_t)n * n;    // [n]
+  double hmax = 0.0;
+  for (int i = 0; i < n; ++i)
+    if (H[(size_t)i * n + i] > hmax) hmax = H[(size_t)i * n + i];
+  const double floor_d = 1e-12 * hmax;
+  for (int j = 0; j < n; ++j) {
+    const double hjj = H[(size_t)j * n + j];
+    const double dj = hjj > floor_d ? hjj : floor_d;  // max(H_jj, 1e-12 max H) (a NaN H_jj meets the pivot test)
+    double p = hjj != hjj ? hjj : hjj + lambda * dj;
+    for (int k = 0; k < j; ++k) p -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
+    if (!(p > 0.0) || !isfinite(p)) return FSDF_ERR_DEGENERATE;
+    const double ljj = sqrt(p);
+    L[(size_t)j * n + j] = ljj;
+    for (int i = j + 1; i < n; ++i) {
+      double s = H[(size_t)i * n + j];
+      for (int k = 0; k < j; ++k) s -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
+      L[(size_t)i * n + j] = s / ljj;
+    }
+  }
+  for (int i = 0; i < n; ++i) {  // L y = g
+    double s = g[i];
+    for (int k = 0; k < i; ++k) s -= L[(size_t)i * n + k] * y[k];
+    y[i] = s / L[(size_t)i * n + i];
+  }
+  for (int i = n - 1; i >= 0; --i) {  // Lᵀ z = y
+    double s = y[i];
+    for (int k = i + 1; k < n; ++k) s -= L[(size_t)k * n + i] * y[k];
+    y[i] = s / L[(size_t)i * n + i];
+  }
+  for (int i = 0; i < n; ++i)
+    if (!isfinite(y[i])) return FSDF_ERR_DEGENERATE;
+  for (int i = 0; i < n; ++i) {
+    const double s = -y[i];
+    const double lo = s < -max_step ? -max_step : s;
+    dx_out[i] = max_step < lo ? max_step : lo;
+  }
+  return FSDF_OK;
+}

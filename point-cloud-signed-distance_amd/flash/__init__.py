@@ -13,7 +13,8 @@ from ._lib import FlashNativeError
 
 __all__ = ["BodyGeometry", "ConvexGeometry", "DeformableInterpolatingSkin", "InterpolatingGeometry",
            "Manipulator", "ManipulatorState", "RigidInterpolatingSkin", "SceneSkin", "hull_poses",
-           "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError"]
+           "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError",
+           "LevenbergMarquardt"]
 
 
 def __getattr__(name):
@@ -24,6 +25,9 @@ def __getattr__(name):
     if name == "Tracking":
         from . import tracking
         return tracking
+    if name == "LevenbergMarquardt":  # the opt-in second-order tracking solver
+        from .tracking import LevenbergMarquardt
+        return LevenbergMarquardt
     if name == "DepthSensors":
         from . import depthsensors
         return depthsensors

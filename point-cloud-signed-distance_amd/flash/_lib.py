@@ -104,6 +104,9 @@ _PROTOS = {
     "fsdf_state_gradient": (c_int32, [c_void_p] + [c_void_p] * 2 + [POINTER(c_double), c_void_p]),
     "fsdf_descend": (c_int32, [c_void_p, c_void_p, c_int32, c_double, c_double, c_double, c_void_p, c_double,
                                POINTER(c_double), POINTER(c_int32)]),
+    "fsdf_gauss_newton_matrix": (c_int32, [c_int32] + [c_void_p] * 7 + [c_int32] + [c_void_p] * 2 + [c_int32] +
+                                 [c_void_p] * 2),
+    "fsdf_lm_step": (c_int32, [c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p]),
 }
 SYMBOLS = tuple(_PROTOS)
 
@@ -167,6 +170,24 @@ def convex_hull(points: np.ndarray):
     if st != FSDF_OK:
         raise FlashNativeError(st, f"fsdf_convex_hull failed on {n} points")
     return verts[: nv.value].copy(), faces[: nf.value].copy(), planes[: nf.value].copy()
+
+
+def lm_step(H, g, damping: float, max_step: float):
+    """fsdf_lm_step: clamp(−(H + damping·diag(D))⁻¹ g, ±max_step) with D_ii =
+    max(H_ii, 1e-12 max_j H_jj), by Cholesky (host only). Returns (status, dx):
+    status 5 (FSDF_ERR_DEGENERATE, dx None) for a non-positive or non-finite
+    pivot; other failures raise."""
+    g = np.ascontiguousarray(g, np.float64).reshape(-1)
+    n = g.size
+    H = np.ascontiguousarray(H, np.float64).reshape(n, n)
+    work = np.empty(n * n + n)
+    dx = np.empty(n)
+    st = load().fsdf_lm_step(n, ptr(H), ptr(g), float(damping), float(max_step), ptr(work), ptr(dx))
+    if st == 5:
+        return st, None
+    if st != FSDF_OK:
+        raise FlashNativeError(st, "fsdf_lm_step: bad arguments")
+    return st, dx
 
 
 class Context:

@@ -287,6 +287,61 @@ class Mechanism:
             raise _lib.FlashNativeError(st, "fsdf_config_gradient: bad tree, configuration or surface bodies")
         return g
 
+    def gauss_newton_matrix(self, q: np.ndarray, surface_body, moments) -> np.ndarray:
+        """A = Σ_k S_b(k) M_k S_b(k)ᵀ [nq, nq] from the per-surface second
+        moments of the residual (moments [S, 21], the upper triangles of
+        Σ w wᵀ over each surface's points, w = (∇d*, p × ∇d*)) — natively
+        (fsdf_gauss_newton_matrix,
+        csrc/gauss_newton.cpp; gauss_newton_matrix_numpy is the test reference).
+        S_b is the map config_gradient applies to a wrench on body b, so
+        2A is the Gauss-Newton Hessian of Σ d*² at the caller's q."""
+        from . import _lib
+        P = self._kinematic_plan()
+        q = np.ascontiguousarray(q, np.float64)
+        self.body_transform_arrays(q)
+        rb_ptr, tb_ptr = self._fk_last[3]
+        nb, nq = self.num_bodies, self._nq
+        sb = np.ascontiguousarray(surface_body, np.int32)
+        mom = np.ascontiguousarray(moments, np.float64).reshape(len(sb), 21)
+        work = np.empty(36 * nb + 6 * nq)
+        A = np.zeros((nq, nq))
+        nat = P["native_ptrs"]
+        st = _lib.load().fsdf_gauss_newton_matrix(nb, nat[0], nat[1], nat[2], nat[3], rb_ptr, tb_ptr, q.ctypes.data,
+                                                  len(sb), sb.ctypes.data, mom.ctypes.data, nq, work.ctypes.data,
+                                                  A.ctypes.data)
+        if st != _lib.FSDF_OK:
+            raise _lib.FlashNativeError(st, "fsdf_gauss_newton_matrix: bad tree, configuration or surface bodies")
+        return A
+
+    def wrench_maps_numpy(self, q: np.ndarray) -> np.ndarray:
+        """S [nb, nq, 6]: S[b] maps a wrench (F, M about the world origin) on
+        body b to config_gradient's ∂c/∂q — column j is config_gradient_numpy
+        of the unit wrench e_j on b (test reference)."""
+        nb = self.num_bodies
+        S = np.zeros((nb, self._nq, 6))
+        for b in range(1, nb):
+            for j in range(6):
+                w = np.zeros((nb, 6))
+                w[b, j] = 1.0
+                S[b, :, j] = self.config_gradient_numpy(q, w)
+        return S
+
+    def gauss_newton_matrix_numpy(self, q: np.ndarray, surface_body, moments) -> np.ndarray:
+        """gauss_newton_matrix in numpy, from config_gradient_numpy on unit
+        wrenches (test reference)."""
+        q = np.asarray(q, np.float64)
+        S = self.wrench_maps_numpy(q)
+        A = np.zeros((self._nq, self._nq))
+        iu = np.triu_indices(6)
+        for k, b in enumerate(surface_body):
+            if b < 0:
+                continue
+            M = np.zeros((6, 6))
+            M[iu] = np.asarray(moments[k], np.float64)
+            M = M + np.triu(M, 1).T
+            A += S[b] @ M @ S[b].T
+        return A
+
     def config_gradient_numpy(self, q: np.ndarray, body_wrench: np.ndarray) -> np.ndarray:
         """The chain rule of config_gradient in numpy (test reference)."""
         nb = self.num_bodies
