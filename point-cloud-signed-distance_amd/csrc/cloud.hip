@@ -1,0 +1,403 @@
+// cloud.hip — the resident cloud of a context: ingest (host, device, ranges,
+// keyed shards), the seeds carried from one cloud to the next, the next
+// frame's prefetch, and the regroup by nearest surface.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "ctx.h"
+
+// Convert/copy AoS f64 points already on the device into a resident buffer of
+// the context precision, growing it when needed.
+int adopt_points_device(fsdf_ctx* c, const double* d_src, int64_t n, fsdf::DevBuf<unsigned char>& dst) {
+  HIPCHECK(c, dst.reserve((size_t)std::max<int64_t>(n, 1) * 3 * point_bytes(c)));
+  if (n == 0) return FSDF_OK;
+  if (c->precision == 64) {
+    HIPCHECK(c, hipMemcpyAsync(dst.get(), d_src, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  } else {
+    HIPCHECK(c, fsdf::launch_to_f32(d_src, (float*)dst.get(), n * 3, c->stream));
+  }
+  return FSDF_OK;
+}
+
+static int finish_resident(fsdf_ctx* c, int64_t n, bool ranged, bool spheres_done = false);
+
+// Seeds for a new cloud's first pass from the last pass over the previous one
+// (fsdf_set_points / fsdf_set_points_prefetched of sorting hull-only contexts):
+// before the cloud is replaced its points write their k* into a coarse voxel
+// grid (carry_seeds_out), after it the new points read theirs into the seed
+// buffer (finish_resident). The grid's box is the first cloud's box grown by
+// a quarter of its extent each way, fixed for the context. Seeds only order
+// the search — the pass's bits do not depend on them (tests/test_gpu_tracking.py).
+static bool seeds_apply(const fsdf_ctx* c) {
+  return FSDF_PRIOR_SEEDS && c->sort_points && c->lm.R == 0 && c->lm.S <= 64 && c->lm.K > 0;
+}
+
+static int ensure_vox_box(fsdf_ctx* c, const double* d_src, int64_t n) {
+  if (c->vox_ok || n <= 0 || !seeds_apply(c)) return FSDF_OK;
+  double* d_box = nullptr;
+  hipError_t e = fsdf::cloud_box(d_src, n, c->sort, c->stream, &d_box);
+  if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "set_points (seed box): %s", hipGetErrorString(e));
+  double box[6];
+  HIPCHECK(c, hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));  // (once per context)
+  for (int j = 0; j < 3; ++j) {
+    const double ext = std::max(box[3 + j] - box[j], 1e-3);
+    if (!std::isfinite(ext)) return FSDF_OK;  // (no seeds)
+    c->vox.lo[j] = box[j] - 0.25 * ext;
+    c->vox.inv[j] = fsdf::kVoxDim / (1.5 * ext);
+  }
+  HIPCHECK(c, c->vox_grid.reserve((size_t)fsdf::kVoxDim * fsdf::kVoxDim * fsdf::kVoxDim));
+  c->vox_ok = true;
+  return FSDF_OK;
+}
+
+static int carry_seeds_out(fsdf_ctx* c) {
+  c->seed_pending = false;
+  if (!c->vox_ok || !seeds_apply(c) || c->n <= 0 || !c->prior_ok || c->prior.capacity() < (size_t)c->n || c->ranged)
+    return FSDF_OK;
+  uint8_t* grid = c->vox_grid.get();
+  HIPCHECK(c, hipMemsetAsync(grid, 0xFF, (size_t)fsdf::kVoxDim * fsdf::kVoxDim * fsdf::kVoxDim, c->stream));
+  hipError_t e = fsdf::vox_scatter(c->precision, c->cur.pts.get(), c->n, c->prior.get(), c->vox, grid, c->stream);
+  if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "set_points (seeds): %s", hipGetErrorString(e));
+  c->seed_pending = true;
+  return FSDF_OK;
+}
+
+// [begin, end): the resident cloud is that range of the whole cloud's order
+// (the Hilbert order of all n points with sort_points, else the caller's);
+// the permutation then holds the points' indices in the whole cloud
+// (fsdf_set_points_range). begin = 0, end = n: the whole cloud.
+static int set_points_impl(fsdf_ctx* c, const double* src, int64_t n, bool device_src, int64_t begin, int64_t end,
+                           bool range_call = false) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n < 0 || (n > 0 && !src)) return fail(c, FSDF_ERR_ARG, "set_points: bad buffer (n=%lld)", (long long)n);
+  if (begin < 0 || end < begin || end > n)
+    return fail(c, FSDF_ERR_ARG, "set_points_range: bad range [%lld, %lld) of %lld points", (long long)begin,
+                (long long)end, (long long)n);
+  if ((c->sort_points || begin > 0 || end < n) && n > INT32_MAX)
+    return fail(c, FSDF_ERR_ARG, "set_points: sorted or ranged clouds support < 2^31 points (n=%lld)", (long long)n);
+  const bool ranged = begin > 0 || end < n;
+  HIPCHECK(c, hipSetDevice(c->device));
+  // the previous frame's work may still read the staging buffer / the cloud
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  int rc0 = ranged ? FSDF_OK : carry_seeds_out(c);  // (the previous cloud, still resident)
+  if (rc0) return rc0;
+  c->n = 0;
+  const double* d_src = src;
+  if (!device_src && n > 0) {
+    HIPCHECK(c, c->staging.reserve((size_t)n * 3));
+    HIPCHECK(c, hipMemcpyAsync(c->staging.get(), src, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice,
+                               c->stream));
+    d_src = c->staging.get();
+  }
+  const int64_t nr = end - begin;  // resident points
+  const size_t tsz = point_bytes(c);
+  auto ensure_res = [&]() -> int {
+    HIPCHECK(c, c->cur.pts.reserve((size_t)std::max<int64_t>(nr, 1) * 3 * tsz));
+    HIPCHECK(c, c->cur.perm.reserve((size_t)std::max<int64_t>(nr, 1)));
+    return FSDF_OK;
+  };
+  if (c->sort_points && n > 0) {
+    // spatially coherent resident order + permutation back to caller order
+    int rc = ensure_res();
+    if (rc) return rc;
+    if (!ranged) {
+      rc = ensure_vox_box(c, d_src, n);
+      if (rc) return rc;
+    }
+    if (!ranged) {
+      hipError_t e = fsdf::sort_points_spatial(d_src, n, c->precision, c->cur.pts.get(), c->cur.perm.get(), c->sort,
+                                               c->stream);
+      if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "set_points (sort): %s", hipGetErrorString(e));
+    } else {
+      // the whole cloud sorted into scratch, then the range kept
+      HIPCHECK(c, c->range_pts.reserve((size_t)n * 3 * tsz));
+      HIPCHECK(c, c->range_perm.reserve((size_t)n));
+      hipError_t e = fsdf::sort_points_spatial(d_src, n, c->precision, c->range_pts.get(), c->range_perm.get(),
+                                               c->sort, c->stream);
+      if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "set_points_range (sort): %s", hipGetErrorString(e));
+      if (nr > 0) {
+        HIPCHECK(c, hipMemcpyAsync(c->cur.pts.get(), c->range_pts.get() + (size_t)begin * 3 * tsz,
+                                   (size_t)nr * 3 * tsz, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(c->cur.perm.get(), c->range_perm.get() + begin, (size_t)nr * sizeof(int32_t),
+                                   hipMemcpyDeviceToDevice, c->stream));
+      }
+    }
+  } else if (ranged) {
+    // a slice of the caller's order; the permutation names the slice's indices
+    int rc = ensure_res();
+    if (rc) return rc;
+    rc = adopt_points_device(c, d_src + 3 * begin, nr, c->cur.pts);
+    if (rc) return rc;
+    std::vector<int32_t> idx((size_t)std::max<int64_t>(nr, 0));
+    for (int64_t i = 0; i < nr; ++i) idx[(size_t)i] = (int32_t)(begin + i);
+    if (nr > 0)
+      HIPCHECK(c, hipMemcpyAsync(c->cur.perm.get(), idx.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (idx is a host temporary)
+  } else {
+    c->cur.perm.reset();  // (no permutation: the resident order is the caller's)
+    int rc = adopt_points_device(c, d_src, n, c->cur.pts);
+    if (rc) return rc;
+  }
+  return finish_resident(c, nr, ranged || range_call);
+}
+
+// the per-cloud state of a new resident cloud of n points (cur.pts / cur.perm
+// written, stream-ordered): chunk spheres (unless spheres_done: a prefetched
+// cloud's came with it), seed buffer, plan and regroup state
+static int finish_resident(fsdf_ctx* c, int64_t n, bool ranged, bool spheres_done) {
+  if (n > 0 && !spheres_done) {  // per-chunk bounding spheres of the resident order (pose-independent)
+    // (padded to whole 4-chunk pass workgroups: every wave of a hull-partitioned
+    // pass reads its chunk's row, also past the cloud's end)
+    const int64_t nc = ((n + 63) / 64 + 3) & ~(int64_t)3;
+    if (c->cur.chunk_ws.capacity() < (size_t)nc * 4) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    HIPCHECK(c, c->cur.chunk_ws.reserve((size_t)nc * 4));
+    HIPCHECK(c, fsdf::launch_chunk_spheres(c->precision, c->cur.pts.get(), n, nc, c->cur.chunk_ws.get(),
+                                           c->stream));
+  }
+  if (n > 0) {
+    // (the previous frame's passes are done: synchronised above; the seed scatter may still read it)
+    if (c->prior.capacity() < (size_t)n) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    HIPCHECK(c, c->prior.reserve((size_t)n));
+  }
+  // a new cloud: its first pass seeds from the previous cloud's voxels, else from the bounds
+  c->prior_ok = false;
+  if (c->seed_pending && n > 0 && !ranged) {
+    hipError_t e = fsdf::vox_gather(c->precision, c->cur.pts.get(), n, c->vox, c->vox_grid.get(), c->prior.get(),
+                                    c->stream);
+    if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "set_points (seeds): %s", hipGetErrorString(e));
+    c->prior_ok = true;
+  }
+  c->seed_pending = false;
+  c->regrouped = false;
+  c->regroup_pending = true;  // (the auto regroup follows the new cloud's first iteration pass)
+  c->last_pass_shape = 0;
+  // the caller may reuse its buffer once this returns
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  c->n = n;
+  // (a range call keeps resident-order outputs even when its range is the
+  // whole cloud: the caller indexes them through the permutation)
+  c->ranged = ranged;
+  c->plan_nc = -1;  // a new cloud: its first planned pass runs the default shape and measures
+  // and its first one-wave pass runs the previous cloud's Hilbert-layout
+  // order and rebuilds it from its own costs (left to age, a stale order cost
+  // the next passes 0.094 -> 0.111 ms, tools/seed_probe.py)
+  c->order_age[0] = kOrderEvery;
+  return FSDF_OK;
+}
+
+// ---- exchanged spatial shards (O(N/W) ingest per rank) ------------------------
+extern "C" int fsdf_cloud_box_device(fsdf_ctx* c, const double* d_xyz, int64_t n, double* box_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n < 0 || (n > 0 && !d_xyz) || !box_out) return fail(c, FSDF_ERR_ARG, "cloud_box_device: bad arguments");
+  HIPCHECK(c, hipSetDevice(c->device));
+  if (n == 0) {
+    for (int j = 0; j < 3; ++j) {
+      box_out[j] = HUGE_VAL;
+      box_out[3 + j] = -HUGE_VAL;
+    }
+    return FSDF_OK;
+  }
+  double* d_box = nullptr;
+  hipError_t e = fsdf::cloud_box(d_xyz, n, c->sort, c->stream, &d_box);
+  if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "cloud_box_device: %s", hipGetErrorString(e));
+  HIPCHECK(c, hipMemcpyAsync(box_out, d_box, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_curve_keys_device(fsdf_ctx* c, const double* d_xyz, int64_t n, const double* box,
+                                      uint32_t* d_keys) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n < 0 || (n > 0 && (!d_xyz || !d_keys)) || !box) return fail(c, FSDF_ERR_ARG, "curve_keys_device: bad arguments");
+  for (int j = 0; j < 6; ++j)
+    if (!std::isfinite(box[j])) return fail(c, FSDF_ERR_ARG, "curve_keys_device: box not finite");
+  HIPCHECK(c, hipSetDevice(c->device));
+  if (n == 0) return FSDF_OK;
+  double* d_box = nullptr;  // (the scratch's box slot, filled from the host)
+  hipError_t e = fsdf::cloud_box(d_xyz, 0, c->sort, c->stream, &d_box);
+  if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "curve_keys_device: %s", hipGetErrorString(e));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));  // (an earlier sort may still read the slot)
+  HIPCHECK(c, hipMemcpy(d_box, box, 6 * sizeof(double), hipMemcpyHostToDevice));
+  e = fsdf::curve_keys(d_xyz, n, d_box, d_keys, c->stream);
+  if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "curve_keys_device: %s", hipGetErrorString(e));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_points_keyed_device(fsdf_ctx* c, const double* d_xyz, const uint32_t* d_keys,
+                                            const int64_t* d_index, int64_t n) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n < 0 || (n > 0 && (!d_xyz || !d_keys || !d_index)))
+    return fail(c, FSDF_ERR_ARG, "set_points_keyed_device: bad arguments");
+  if (n > INT32_MAX) return fail(c, FSDF_ERR_ARG, "set_points_keyed_device: < 2^31 points per shard");
+  HIPCHECK(c, hipSetDevice(c->device));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  c->n = 0;
+  HIPCHECK(c, c->cur.pts.reserve((size_t)std::max<int64_t>(n, 1) * 3 * point_bytes(c)));
+  HIPCHECK(c, c->cur.perm.reserve((size_t)std::max<int64_t>(n, 1)));
+  if (n > 0) {
+    hipError_t e = fsdf::sort_points_keyed(d_xyz, d_keys, d_index, n, c->precision, c->cur.pts.get(),
+                                           c->cur.perm.get(), c->sort, c->stream);
+    if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "set_points_keyed_device (sort): %s", hipGetErrorString(e));
+  }
+  return finish_resident(c, n, true);
+}
+
+extern "C" int fsdf_set_points(fsdf_ctx* c, const double* xyz, int64_t n) {
+  return set_points_impl(c, xyz, n, false, 0, n);
+}
+
+extern "C" int fsdf_set_points_device(fsdf_ctx* c, const double* d_xyz, int64_t n) {
+  return set_points_impl(c, d_xyz, n, true, 0, n);
+}
+
+// The next frame's cloud ahead of time: its host-to-device copy runs on a
+// stream of the context's own while the current frame's passes run on the
+// context stream (the copy engine beside the compute units), and
+// fsdf_set_points_prefetched then makes it resident from the device copy —
+// the per-frame ingest loses its host-link transfer (25 MB at 2^20 points).
+// The copy overlaps only from page-locked host memory; the caller keeps xyz
+// unchanged until fsdf_set_points_prefetched returns. A second prefetch
+// replaces a pending one. fsdf_prefetch_points only records the cloud;
+// prefetch_issue enqueues the copy and sort on the copy stream, from the next
+// pass's launch (run_pass) or from fsdf_set_points_prefetched when no pass
+// came between.
+int prefetch_issue(fsdf_ctx* c) {
+  c->prefetch_deferred = false;
+  const double* xyz = c->prefetch_src;
+  const int64_t n = c->prefetch_n;
+  HIPCHECK(c, hipSetDevice(c->device));
+  // (an earlier prefetch's copy may still write the buffer; a consumed one's
+  // sort has finished: fsdf_set_points_prefetched returns after it)
+  HIPCHECK(c, hipStreamSynchronize(c->copy_stream));
+  if (n > 0) {
+    HIPCHECK(c, c->prefetch.reserve((size_t)n * 3));
+    HIPCHECK(c, hipMemcpyAsync(c->prefetch.get(), xyz, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice,
+                               c->copy_stream));
+  }
+  // the next resident cloud, Hilbert-sorted on the copy stream as well (its own
+  // buffers and sort scratch: the current frame's cloud is untouched), so the
+  // next frame's set_points_prefetched only swaps buffers
+  c->prefetch_sorted = false;
+  if (n > 0 && c->sort_points && n <= INT32_MAX) {
+    const int64_t nc = ((n + 63) / 64 + 3) & ~(int64_t)3;  // (finish_resident's padding)
+    ResidentCloud& nx = c->next;
+    HIPCHECK(c, nx.pts.reserve((size_t)n * 3 * point_bytes(c)));
+    HIPCHECK(c, nx.perm.reserve((size_t)n));
+    HIPCHECK(c, nx.chunk_ws.reserve((size_t)nc * 4));
+    hipError_t e = fsdf::sort_points_spatial(c->prefetch.get(), n, c->precision, nx.pts.get(), nx.perm.get(),
+                                             c->sort_next, c->copy_stream);
+    if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "prefetch_points (sort): %s", hipGetErrorString(e));
+    HIPCHECK(c, fsdf::launch_chunk_spheres(c->precision, nx.pts.get(), n, nc, nx.chunk_ws.get(), c->copy_stream));
+    c->prefetch_sorted = true;
+  }
+  HIPCHECK(c, hipEventRecord(c->ev_prefetch, c->copy_stream));
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_prefetch_points(fsdf_ctx* c, const double* xyz, int64_t n) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n < 0 || (n > 0 && !xyz)) return fail(c, FSDF_ERR_ARG, "prefetch_points: bad buffer (n=%lld)", (long long)n);
+  c->prefetch_src = xyz;
+  c->prefetch_n = n;
+  c->prefetch_deferred = true;
+  c->prefetch_rc = FSDF_OK;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_points_prefetched(fsdf_ctx* c) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->prefetch_n < 0) return fail(c, FSDF_ERR_STATE, "set_points_prefetched: no prefetch pending");
+  const int64_t n = c->prefetch_n;
+  int rc = c->prefetch_deferred ? prefetch_issue(c) : c->prefetch_rc;
+  c->prefetch_n = -1;
+  c->prefetch_rc = FSDF_OK;
+  if (rc) return rc;
+  HIPCHECK(c, hipSetDevice(c->device));
+  HIPCHECK(c, hipStreamWaitEvent(c->stream, c->ev_prefetch, 0));  // (the copy, and the sort when done there)
+  if (!c->prefetch_sorted) return set_points_impl(c, c->prefetch.get(), n, true, 0, n);
+  // the sorted next cloud becomes resident: the current frame's work is done
+  // (synchronised), its buffers become the next prefetch's
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  rc = ensure_vox_box(c, c->prefetch.get(), n);  // (a first cloud: the seed box)
+  if (rc) return rc;
+  rc = carry_seeds_out(c);  // (the previous cloud, still resident)
+  if (rc) return rc;
+  c->n = 0;
+  std::swap(c->cur, c->next);
+  return finish_resident(c, n, false, true);
+}
+
+extern "C" int fsdf_set_points_range(fsdf_ctx* c, const double* xyz, int64_t n, int64_t begin, int64_t end) {
+  return set_points_impl(c, xyz, n, false, begin, end, true);
+}
+
+extern "C" int fsdf_set_points_range_device(fsdf_ctx* c, const double* d_xyz, int64_t n, int64_t begin,
+                                            int64_t end) {
+  return set_points_impl(c, d_xyz, n, true, begin, end, true);
+}
+
+// Regroup the resident cloud by each point's nearest surface in the last pass
+// (a stable device sort on PassOutputs::prior_out's bytes: the Hilbert order
+// kept within each group), so that a chunk's points share their surface and
+// the seeded passes evaluate fewer hulls per chunk. Per-point results do not
+// change; sums change in rounding only (other chunks). Stream-ordered after
+// the passes already queued.
+extern "C" int fsdf_regroup_points(fsdf_ctx* c) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->n == 0) return FSDF_OK;
+  if (!c->cur.perm.get())
+    return fail(c, FSDF_ERR_STATE, "regroup_points: needs a sorted (sort_points) or ranged resident cloud");
+  if (!c->prior_ok || c->prior.capacity() < (size_t)c->n)
+    return fail(c, FSDF_ERR_STATE, "regroup_points: run a pass over the resident cloud first (hull-only scenes)");
+  HIPCHECK(c, hipSetDevice(c->device));
+  hipError_t e =
+      fsdf::regroup_points(c->cur.pts, c->n, c->precision, c->cur.perm.get(), c->prior.get(), c->sort, c->stream);
+  if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "regroup_points: %s", hipGetErrorString(e));
+  const int64_t nc = ((c->n + 63) / 64 + 3) & ~(int64_t)3;
+  HIPCHECK(c, fsdf::launch_chunk_spheres(c->precision, c->cur.pts.get(), c->n, nc, c->cur.chunk_ws.get(), c->stream));
+  c->plan_nc = -1;  // other chunks: the next planned pass measures anew
+  // the one-wave grid's heaviest-first block order: the next pass runs the
+  // regrouped layout's order (the previous frame's) and rebuilds it from its
+  // own costs — unordered, that pass took 163 us, with the Hilbert layout's
+  // order 177, with the previous regrouped one 122 (M64 2^20, profiles/r06/regroup_order/)
+  c->order_age[1] = kOrderEvery;
+  c->regrouped = true;
+  c->regroup_pending = false;
+  return FSDF_OK;
+}
+
+// The auto rule (FSDF_REGROUP_AUTO): regroup where the pass is bound by its
+// summed work — the last resident pass ran one wave per chunk (the grid above
+// the planned window) — and not where the planned pass or a hull-partitioned
+// tier is bound by its heaviest chunk, which grouping makes heavier (2^17 step
+// 0.0612 -> 0.0677 ms and worse). Needs a pass over the
+// cloud (its k* are the groups) and a sorted or ranged cloud.
+static bool regroup_wanted(const fsdf_ctx* c) {
+  return c->n > 0 && c->cur.perm.get() && c->prior_ok && !c->regrouped && c->last_pass_shape == 1;
+}
+
+extern "C" int fsdf_regroup_auto(fsdf_ctx* c, int32_t* applied_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (applied_out) *applied_out = 0;
+  if (!regroup_wanted(c)) return FSDF_OK;
+  const int rc = fsdf_regroup_points(c);
+  if (rc) return rc;
+  if (applied_out) *applied_out = 1;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_regroup(fsdf_ctx* c, int32_t mode) {
+  if (!c) return FSDF_ERR_ARG;
+  if (mode != FSDF_REGROUP_OFF && mode != FSDF_REGROUP_AUTO)
+    return fail(c, FSDF_ERR_ARG, "set_regroup: unknown mode %d", mode);
+  c->regroup_mode = mode;
+  return FSDF_OK;
+}

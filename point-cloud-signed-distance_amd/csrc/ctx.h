@@ -1,0 +1,254 @@
+// ctx.h — the context behind include/flashsdf.h, shared by the host-side
+// translation units: capi.hip (context, model, queries), cloud.hip (resident
+// cloud), pass.hip (the residual pass), iterate.hip (mechanism, solver loops).
+//
+// The context owns its device and pinned memory in the buffers of
+// device_buffers.h (see the rule there: a pointer is read with get() after the
+// reserve for that use). LocalModel, PosedModel and ChunkOutputs are views of
+// them, filled where the buffers are reserved.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdio.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "device_buffers.h"
+#include "flashsdf.h"
+#include "fsdf_internal.h"
+
+#ifndef FSDF_POSE_OVERLAP
+#define FSDF_POSE_OVERLAP 0  // (pose_model: measured slower, off)
+#endif
+#ifndef FSDF_PRIOR_SEEDS
+#define FSDF_PRIOR_SEEDS 1
+#endif
+#ifndef FSDF_ORDER_EVERY
+#define FSDF_ORDER_EVERY 16
+#endif
+#ifndef FSDF_CHUNK_WS
+#define FSDF_CHUNK_WS 1  // passes over the resident cloud read the chunk spheres of set_points
+#endif
+// fsdf_value_and_gradient: the reduction kernel stores the accumulator into
+// the pinned host buffer itself (no D2H copy command before the sync). Same
+// results; full iteration -1.5 to -2.5 us against the pinned copy
+// (profiles/r02/experiments/r02zc).
+#ifndef FSDF_ZERO_COPY_ACCUM
+#define FSDF_ZERO_COPY_ACCUM 1
+#endif
+constexpr int kOrderEvery = FSDF_ORDER_EVERY;
+constexpr int kPoseRing = 8;
+
+// (the context's types and the functions shared by its translation units are
+// internal: not exported)
+#pragma GCC visibility push(hidden)
+// device arrays of the local model (fsdf::LocalModel is their view) and the
+// buffers sized by it
+struct ModelBuffers {
+  fsdf::DevBuf<double> verts_l, planes_l, sphere_l, box_l;
+  fsdf::DevBuf<int32_t> faces, face_hull, face_off, vert_hull, vert_off, face_rows, hull_surface, item_meta,
+      surface_kind, rbf_surface, rbf_row_off, rbf_acc_off;
+  fsdf::DevBuf<double> rbf64;  // per-pass RBF rows (f64)
+  fsdf::DevBuf<double> poses, accum;
+};
+// storage of one fsdf::PosedModel (T arrays in bytes)
+struct PosedBuffers {
+  fsdf::DevBuf<unsigned char> verts_w, hscale_w, planes_w, image_w;
+  fsdf::DevBuf<float> spheres_w, screen_w;
+};
+// storage of fsdf::ChunkOutputs and the plan kernel's scratch
+struct ChunkBuffers {
+  fsdf::DevBuf<int32_t> hdr;
+  fsdf::DevBuf<double> rows;  // ent | csum | dense: one allocation
+  fsdf::DevBuf<uint32_t> dur;
+  fsdf::DevBuf<int32_t> plan_order;
+};
+// a resident cloud: points (precision-typed AoS, bytes), resident i -> caller
+// index (sorted / ranged clouds; none: the resident order is the caller's),
+// [ceil(n/64)][4] bounding sphere per 64-point chunk
+struct ResidentCloud {
+  fsdf::DevBuf<unsigned char> pts;
+  fsdf::DevBuf<int32_t> perm;
+  fsdf::DevBuf<float> chunk_ws;
+};
+
+struct fsdf_ctx {
+  int device = 0;
+  int precision = 64;
+  int sort_points = 0;
+  int cull = 1;
+  int out_order = FSDF_ORDER_CALLER;
+  // streams and events ahead of the buffers: destroyed after them
+  fsdf::Stream own_stream;
+  hipStream_t stream = nullptr;  // own_stream or the caller's (fsdf_set_stream)
+  fsdf::Stream pose_stream, copy_stream;
+  fsdf::Event ev_pose, ev_pm_free[2], ev_prefetch;
+  fsdf::Event pose_ev[kPoseRing], rbf_ev[kPoseRing];
+  std::vector<fsdf::Event> prof_ev;  // pass-kernel timing (fsdf_profile_pass): triples
+  std::string err;
+  std::string pass_kernel;  // the pass-kernel variant of the last pass (fsdf_pass_kernel_name)
+
+  // local model
+  fsdf::LocalModel lm;
+  ModelBuffers model;
+  fsdf::PinnedBuf<double> h_rbf[kPoseRing];  // pinned staging ring for RBF rows (own slots and events,
+                                             // independent of the pose ring: poses of <= 64
+                                             // surfaces never touch theirs)
+  std::vector<int32_t> h_surface_kind, h_n_centers;  // host copy of the surface list (set_surfaces)
+  int rbf_slot = 0;
+  bool rbf_ready = false;
+  // posed model, double-buffered: pass i poses into buffer i % 2 on its own
+  // stream while the context stream still runs pass i-1 / its reduce
+  // (FSDF_POSE_OVERLAP); ev_pm_free[b] marks the last read of buffer b
+  fsdf::PosedModel pm, pm_alt;
+  PosedBuffers posed[2];
+  fsdf::DevBuf<float> rbf32;  // the per-pass RBF rows of f32 contexts (both posed models' rbf_rows)
+  int pm_next = 0;
+  // poses: pinned ring + device copy (model.poses)
+  fsdf::PinnedBuf<double> h_poses[kPoseRing];
+  int pose_slot = 0;
+  // pinned read-back of the accumulator (fetch): a pageable destination makes
+  // the D2H copy go through the runtime's staging buffer
+  fsdf::PinnedBuf<double> h_acc;
+  // resident cloud
+  int64_t n = 0;
+  ResidentCloud cur;
+  fsdf::DevBuf<uint8_t> prior;       // [n] each resident point's nearest surface in the last pass (seed hint)
+  bool prior_ok = false;             // prior was written by a pass over the current resident cloud
+  // regroup (fsdf_regroup_points): mode (fsdf_set_regroup), whether the
+  // resident cloud has been regrouped since its set_points, whether its first
+  // iteration pass is still to come (the auto regroup follows that pass), and
+  // the shape of the last resident pass (the auto rule's input)
+  int regroup_mode = FSDF_REGROUP_AUTO;
+  bool regrouped = false;
+  bool regroup_pending = false;
+  int last_pass_shape = 0;           // 0 none, 1 one wave per chunk, 2 hull-partitioned tiers, 3 planned
+  fsdf::SortScratch sort;            // per-frame sort scratch (grown only)
+  fsdf::DevBuf<double> staging;      // host-source clouds land here first
+  // the next frame's cloud, copied ahead on a stream of its own (fsdf_prefetch_points)
+  fsdf::DevBuf<double> prefetch;
+  int64_t prefetch_n = -1;           // -1: none pending
+  // a prefetch is queued on the next pass's launch (its host-side work then
+  // overlaps that pass instead of delaying the frame's first launch): the
+  // caller's cloud, whether it is still to be issued, and the issue's result
+  const double* prefetch_src = nullptr;
+  bool prefetch_deferred = false;
+  int prefetch_rc = 0;
+  // ... and its resident form, sorted there too (swapped in by fsdf_set_points_prefetched)
+  bool prefetch_sorted = false;
+  ResidentCloud next;
+  fsdf::SortScratch sort_next;
+  // seeds carried from one cloud to the next (a voxel grid of the last pass's k*)
+  fsdf::DevBuf<uint8_t> vox_grid;
+  bool vox_ok = false, seed_pending = false;
+  fsdf::VoxBox vox;
+  bool ranged = false;               // the resident cloud is a range of a larger one (fsdf_set_points_range)
+  fsdf::DevBuf<unsigned char> range_pts;  // fsdf_set_points_range: the whole cloud, sorted (scratch)
+  fsdf::DevBuf<int32_t> range_perm;
+  // work
+  fsdf::DevBuf<double> partials;
+  // cost-ordered schedule of resident-cloud passes (fsdf::PassOutputs::order)
+  fsdf::DevBuf<uint32_t> block_cost;  // [kMaxBlocks]
+  // the one-wave grid's heaviest-first block orders, one per layout of a frame's
+  // cloud: [0] its Hilbert order (the frame's first pass), [1] regrouped (the
+  // rest of the frame) — each rebuilt from the costs of a pass in its layout, so
+  // a frame's passes run the order the previous frame left for the same layout
+  fsdf::DevBuf<int32_t> block_order[2];  // [kMaxBlocks]
+  int order_nblocks[2] = {0, 0};  // grid the order was built for (0: none yet)
+  int order_age[2] = {0, 0};      // passes since the order was rebuilt
+  // planned pass (fsdf::planned_pass_kernel): per-chunk partial rows, chunk
+  // durations and the workgroup plan built from them (fsdf_set_plan)
+  fsdf::ChunkOutputs co;             // view of chunk, [co.cap] chunks
+  ChunkBuffers chunk;
+  int co_s = 0;                      // surfaces the dense rows of co were sized for
+  fsdf::DevBuf<int32_t> plan;        // [grid][4]
+  int plan_grid = 0;                 // workgroups of the current plan (0: none — the default shape)
+  int64_t plan_nc = -1;              // chunks the plan was built for
+  int plan_age = 0;                  // planned passes since the plan was rebuilt
+  int plan_enable = 1;
+  double plan_f4 = -1.0, plan_f2 = -1.0;  // shares of the chunks split over 4 / 2 waves (< 0: default counts)
+  int wave_slots = 0;                // device wave slots at the pass's occupancy (0: not queried yet)
+  int64_t plan_max_points = -1;      // planned pass up to this cloud size (per device; -1: the model's default)
+  fsdf::DevBuf<int32_t> kstar;       // per-point outputs (fsdf_eval, fsdf_skin, fsdf_raycast)
+  fsdf::DevBuf<double> d, grad;
+  // query scratch (fsdf_skin)
+  fsdf::DevBuf<unsigned char> q;
+  fsdf::DevBuf<double> q64;
+  bool profiling = false;
+  size_t prof_used = 0;             // events recorded (3 per pass)
+  fsdf::DevBuf<unsigned long long> stats;  // fsdf_kernel_stats
+  bool stats_on = false;
+  // mechanism of fsdf_set_mechanism (host arrays; fsdf_value_and_gradient)
+  struct Mechanism {
+    int nb = 0, nq = 0;
+    std::vector<int32_t> parent, kind, qoff, surface_body;
+    std::vector<double> axis, AR, At, BR, Bt, frame_R, frame_t;
+    std::vector<double> R, t, Rb, tb, poses, accum, work;  // scratch
+    // RBF surfaces (fsdf_set_rbf_centres), in surface order; n == 0: undeclared
+    struct Rbf {
+      int n_sp = 0, n = 0;
+      std::vector<int32_t> body, drow, piv;
+      std::vector<double> local, values, centres, u, lu, G, work;
+    };
+    std::vector<Rbf> rbf;
+    int n_deform = 0;
+    double weight = 10.0;  // default_deformation_cost_weight (src/gradientdescent.jl:7)
+    std::vector<double> rows, body_wrench, x_prepared;
+    // the x of the last two fsdf_eval_state_device passes (their accumulators
+    // may still be in flight): fsdf_state_gradient accepts only these (or the
+    // last prepared x) and refuses any other with FSDF_ERR_STATE
+    std::vector<double> x_pass[2];
+    int x_pass_next = 0;
+  } mech;
+  // device solver loop of fsdf_descend (solver.hip): the mechanism's device
+  // arrays (built on the first device descend after fsdf_set_mechanism) and
+  // one frame's state; pinned staging for x / divisors in and x, f, flags out
+  int solver_device = 1;             // fsdf_set_solver: 1 device where possible (default), 0 host loop,
+                                     // 2 device required; 3 / 4: as 1 / 2 with RBF
+                                     // and deformable scenes admitted
+  bool solver_tree_ok = false;
+  fsdf::SolverTree stree;
+  fsdf::DevBuf<double> stree_blob;   // the tree blob (fsdf::SolverTree::blob)
+  fsdf::DevBuf<double> solver;       // x | div | Rb | tb | poses | f
+  fsdf::DevBuf<int> solver_flags;
+  fsdf::PinnedBuf<double> h_solver;  // pinned: x | div | f | flags (as doubles)
+};
+
+static inline int fail(fsdf_ctx* c, int code, const char* fmt, ...) {
+  if (c) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    c->err = buf;
+  }
+  return code;
+}
+
+#define HIPCHECK(ctx, expr)                                                                             \
+  do {                                                                                                  \
+    hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess) return fail((ctx), FSDF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+static inline int accum_len(const fsdf_ctx* c) { return 1 + 6 * c->lm.S + c->lm.rbf_acc; }
+static inline size_t point_bytes(const fsdf_ctx* c) { return c->precision == 64 ? sizeof(double) : sizeof(float); }
+
+// file-local functions that cross the translation units
+// cloud.hip
+int adopt_points_device(fsdf_ctx* c, const double* d_src, int64_t n, fsdf::DevBuf<unsigned char>& dst);
+int prefetch_issue(fsdf_ctx* c);
+// pass.hip
+int pose_model(fsdf_ctx* c, const double* poses, fsdf::PosedModel** out, int* buf, bool posed = false);
+int release_posed(fsdf_ctx* c, int buf);
+int run_pass(fsdf_ctx* c, const double* poses, const void* d_pts, int64_t n, double* d_accum, int32_t* d_kstar,
+             double* d_d, double* d_grad, const int32_t* d_perm, bool schedule, bool posed = false,
+             const int* skip = nullptr);
+int ensure_outputs(fsdf_ctx* c, int64_t n);
+int ensure_host_acc(fsdf_ctx* c, int len);
+int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
+          double* grad_out, bool want_pp);
+#pragma GCC visibility pop

@@ -34,6 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_buffers.h"
+
 namespace fsdf {
 
 // fp32-screened plane max in f64 contexts (sdf_kernels.hip screen_plane_max);
@@ -163,7 +165,7 @@ struct ChunkOutputs {
   int dparts = 1;              // waves per chunk without a plan (4, 2 or 1)
   // a split chunk's wall time x (num / den) is its serial-equivalent duration
   // (the speed-up of the 4- / 2-wave split; set per model by the context:
-  // capi.hip run_planned, tools/split_speedup.py)
+  // pass.hip run_planned, tools/split_speedup.py)
   int r4n = 5, r4d = 2, r2n = 8, r2d = 5;
   int64_t cap = 0;             // chunks allocated: csum = ent + 24 cap, dense = ent + 25 cap (one allocation
                                // of (25 + 6 S) doubles per chunk: 1.6 KB per chunk at S = 64, i.e. 13 MB at
@@ -234,18 +236,15 @@ size_t pass_lds_bytes(const LocalModel& lm, bool raycast, bool alias = false);
 
 // Scratch of the per-frame spatial sort, owned by the context and grown only
 // (a frame makes no allocation).
-struct SortScratch {
-  double* part = nullptr;  // bbox partials [256][6] + the final box [6]
-  uint32_t* k0 = nullptr;  // keys, double-buffered
-  uint32_t* k1 = nullptr;
-  int32_t* i1 = nullptr;   // alternate index buffer
-  void* tmp = nullptr;     // rocPRIM temporary storage
-  void* pts = nullptr;     // (regroup_points) the cloud buffer the regrouped points go to
-  uint64_t* q0 = nullptr;  // (sort_points_keyed) composite keys, double-buffered
-  uint64_t* q1 = nullptr;
-  size_t part_cap = 0, k_cap0 = 0, k_cap1 = 0, i_cap1 = 0, tmp_cap = 0, pts_cap = 0, q_cap0 = 0, q_cap1 = 0;
+struct __attribute__((visibility("hidden"))) SortScratch {
+  DevBuf<double> part;         // bbox partials [256][6] + the final box [6]
+  DevBuf<uint32_t> k0;         // keys, double-buffered
+  DevBuf<unsigned char> k1;    // (bytes: the alternate keys; regroup_points' priors)
+  DevBuf<int32_t> i1;          // alternate index buffer
+  DevBuf<unsigned char> tmp;   // rocPRIM temporary storage
+  DevBuf<unsigned char> pts;   // (regroup_points) the cloud buffer the regrouped points go to
+  DevBuf<uint64_t> q0, q1;     // (sort_points_keyed) composite keys, double-buffered
 };
-void free_sort_scratch(SortScratch& s);
 
 // Hilbert-order (sort.hip) the f64 AoS cloud d_src into d_dst (context
 // precision) and write the permutation d_perm[resident i] = caller index
@@ -255,14 +254,13 @@ hipError_t sort_points_spatial(const double* d_src, int64_t n, int precision, vo
 // Regroup a resident cloud by each point's nearest surface in the last pass
 // (prior[i] < 64), keeping the current (Hilbert) order within each group: a
 // stable counting sort (sort.hip regroup_*_kernel, three launches). The
-// regrouped points replace *d_pts (the old buffer becomes the scratch's:
-// *d_pts / *pts_cap are updated); d_perm and prior are permuted in place.
-// Asynchronous on `st`.
-hipError_t regroup_points(void** d_pts, int64_t* pts_cap, int64_t n, int precision, int32_t* d_perm, uint8_t* prior,
+// regrouped points replace pts (it swaps with the scratch's buffer: read
+// pts.get() anew); d_perm and prior are permuted in place. Asynchronous on `st`.
+hipError_t regroup_points(DevBuf<unsigned char>& pts, int64_t n, int precision, int32_t* d_perm, uint8_t* prior,
                           SortScratch& s, hipStream_t st);
 // ---- device solver iteration (solver.hip) ------------------------------------
 // The mechanism of a rigid scene as two device buffers built by the context
-// from fsdf_set_mechanism (capi.hip build_solver_tree) — integers and doubles,
+// from fsdf_set_mechanism (iterate.hip build_solver_tree) — integers and doubles,
 // each array at an offset — with the level schedules of the parallel FK and
 // chain rule. The solver kernels copy both buffers into LDS first, so every
 // later access in their level loops is an LDS access.

@@ -1,0 +1,366 @@
+// pass.hip — one residual pass of a context (pose -> pass -> reduce): the
+// partial sums, the pose ring, the planned pass and its plan, the per-point
+// outputs and their read-back, fsdf_eval / fsdf_eval_device and the
+// permutation getters.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "ctx.h"
+
+// default plan composition: chunks split over 4 / 2 waves (fsdf_set_plan shares < 0)
+static constexpr int64_t kPlanDefault4 = 96, kPlanDefault2 = 192;
+
+static int ensure_partials(fsdf_ctx* c, int nblocks) {
+  // (rounded up to whole 8-entry tiles: FSDF_PARTIALS_LAYOUT 2)
+  const size_t need = (size_t)((accum_len(c) + 7) & ~7) * nblocks;
+  HIPCHECK(c, c->partials.reserve(need));
+  return FSDF_OK;
+}
+
+static int upload_poses(fsdf_ctx* c, const double* poses, hipStream_t st) {
+  for (int i = 0; i < 12 * c->lm.S; ++i)
+    if (!std::isfinite(poses[i])) return fail(c, FSDF_ERR_ARG, "poses: entry %d is not finite", i);
+  if (c->lm.S <= fsdf::kPoseArgMax) return FSDF_OK;  // they ride in the pose kernel's arguments
+  const int s = c->pose_slot;
+  c->pose_slot = (s + 1) % kPoseRing;
+  HIPCHECK(c, hipEventSynchronize(c->pose_ev[s]));  // slot free once its last copy ran
+  memcpy(c->h_poses[s].get(), poses, (size_t)c->lm.S * 12 * sizeof(double));
+  HIPCHECK(c, hipMemcpyAsync(c->model.poses.get(), c->h_poses[s].get(), (size_t)c->lm.S * 12 * sizeof(double),
+                             hipMemcpyHostToDevice, st));
+  HIPCHECK(c, hipEventRecord(c->pose_ev[s], st));
+  return FSDF_OK;
+}
+
+// Pose the model for one pass into the next posed buffer. With
+// FSDF_POSE_OVERLAP the upload and pose kernel run on the context's pose
+// stream — behind the last reader of that buffer (two passes back), ahead of
+// the current pass's kernels on the context stream, which waits for them — so
+// the pose kernel overlaps the previous pass's tail and reduce. *buf: the
+// buffer index to release with release_posed() after its last reader.
+// Measured: the cross-stream event waits cost more than the overlap saves
+// (+10 us per step on M64), so it is off and the pose kernel runs in order.
+// posed: the model is already posed on the device (the device solver loop's
+// step poses the next pass's model itself, solver.hip): no pose launch.
+int pose_model(fsdf_ctx* c, const double* poses, fsdf::PosedModel** out, int* buf, bool posed) {
+  const int b = FSDF_POSE_OVERLAP ? c->pm_next : 0;
+  c->pm_next ^= FSDF_POSE_OVERLAP ? 1 : 0;
+  fsdf::PosedModel* P = b ? &c->pm_alt : &c->pm;
+  P->rbf_rows = c->pm.rbf_rows;  // per-pass RBF rows: one buffer, context-stream ordered
+  const hipStream_t ps = FSDF_POSE_OVERLAP ? c->pose_stream : c->stream;
+  if (FSDF_POSE_OVERLAP) HIPCHECK(c, hipStreamWaitEvent(ps, c->ev_pm_free[b], 0));
+  if (!posed) {
+    int rc = upload_poses(c, poses, ps);
+    if (rc) return rc;
+    HIPCHECK(c, fsdf::launch_pose(c->precision, c->lm, c->model.poses.get(), *P, ps,
+                                  c->lm.S <= fsdf::kPoseArgMax ? poses : nullptr));
+  }
+  if (FSDF_POSE_OVERLAP) {
+    HIPCHECK(c, hipEventRecord(c->ev_pose, ps));
+    HIPCHECK(c, hipStreamWaitEvent(c->stream, c->ev_pose, 0));
+  }
+  *out = P;
+  *buf = b;
+  return FSDF_OK;
+}
+
+int release_posed(fsdf_ctx* c, int buf) {
+  if (FSDF_POSE_OVERLAP) HIPCHECK(c, hipEventRecord(c->ev_pm_free[buf], c->stream));
+  return FSDF_OK;
+}
+
+
+static int ensure_chunk_outputs(fsdf_ctx* c, int64_t nc) {
+  if (c->co.cap >= nc && c->co_s >= c->lm.S) return FSDF_OK;
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  c->co = fsdf::ChunkOutputs();
+  c->chunk = ChunkBuffers();  // (all four anew, at this cloud's chunk count)
+  c->plan_nc = -1;
+  HIPCHECK(c, c->chunk.hdr.reserve((size_t)nc * 4));
+  // one allocation: entries [nc][24] | Σ d² [nc] | dense rows [nc][S][6] (sized by the surface count:
+  // (25 + 6 S) doubles per chunk, 1.6 KB at S = 64 — per context, so two in flight hold it twice)
+  HIPCHECK(c, c->chunk.rows.reserve((size_t)nc * (24 + 1 + 6 * (size_t)c->lm.S)));
+  c->co_s = c->lm.S;
+  HIPCHECK(c, c->chunk.dur.reserve((size_t)nc));
+  HIPCHECK(c, c->chunk.plan_order.reserve((size_t)nc));
+  c->co.hdr = c->chunk.hdr.get();
+  c->co.ent = c->chunk.rows.get();
+  c->co.csum = c->co.ent + (size_t)nc * 24;
+  c->co.dense = c->co.ent + (size_t)nc * 25;
+  c->co.dur = c->chunk.dur.get();
+  c->co.cap = nc;
+  return FSDF_OK;
+}
+
+// the plan's composition for nc chunks: n4 chunks over 4 waves, n2 over 2,
+// the rest one wave each. The heaviest `plan_f4` / `plan_f2` shares are split,
+// and at least as many chunks over 4 waves as the device's idle wave slots
+// allow (slots - nc, 3 extra waves per split chunk): a strong-scaling shard
+// that leaves slots free splits its heavy third, a full machine only its tail.
+static int wave_slots(fsdf_ctx* c) {
+  if (c->wave_slots == 0) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0)
+      cus = 256;
+    c->wave_slots = cus * 4 * 4;  // 4 SIMDs x 4 waves (the pass's register budget)
+  }
+  return c->wave_slots;
+}
+
+static void plan_shape(fsdf_ctx* c, int64_t nc, int* n4, int* n2) {
+  wave_slots(c);
+  const int64_t spare = std::max<int64_t>(0, (int64_t)c->wave_slots - nc);
+  // default (shares < 0): fixed counts — the heavy tail that outlasts the rest
+  // of a pass is ~100 chunks at 2^18 and at 2^19 points alike (measured)
+  const int64_t want4 = c->plan_f4 < 0 ? kPlanDefault4 : llround(c->plan_f4 * (double)nc);
+  const int64_t want2 = c->plan_f2 < 0 ? kPlanDefault2 : llround(c->plan_f2 * (double)nc);
+  const int64_t a = std::min<int64_t>(nc, std::max<int64_t>(want4, spare / 3));
+  *n4 = (int)a;
+  *n2 = (int)std::min<int64_t>(nc - a, want2);
+}
+
+// The planned pass of a resident cloud: per-chunk partial rows, the
+// two-level chunk reduction (16-chunk groups, then the tile reduce), and a
+// plan rebuilt from this pass's chunk durations on the first pass of a cloud
+// and then every kOrderEvery passes.
+static int run_planned(fsdf_ctx* c, const fsdf::PosedModel& P, const void* d_pts, int64_t n, double* d_accum,
+                       fsdf::PassOutputs& out, const fsdf::Event* pe, const int* skip) {
+  const int64_t nc = (n + 63) / 64;
+  int rc = ensure_chunk_outputs(c, nc);
+  if (rc) return rc;
+  rc = ensure_partials(c, (int)std::max<int64_t>(fsdf::pass_blocks(n, c->lm), fsdf::reduce_chunk_groups(nc)));
+  if (rc) return rc;
+  out.partials = c->partials.get();
+  out.cost = nullptr;
+  out.order = nullptr;
+  fsdf::ChunkOutputs co = c->co;
+  // the split speed-ups behind the serial-equivalent durations (plan order,
+  // fsdf_chunk_costs, the shard rebalance): M64-class scenes (>= 32 hulls)
+  // measured 1.82-1.87x at 4 waves and 1.28-1.33x at 2 (tools/split_speedup.py,
+  // profiles/r05/split_speedup.jsonl); IRB140-class measurements scattered
+  // (4-way 1.22-1.53x) and their plan ran slower with them (profiles/r05/
+  // keyed_plan), so those keep round 4's 5/2 and 8/5
+  if (c->lm.K >= 32) {
+    co.r4n = 15; co.r4d = 8; co.r2n = 4; co.r2d = 3;
+  }
+  const bool planned = c->plan_nc == nc && c->plan_grid > 0;
+  co.plan = planned ? c->plan.get() : nullptr;
+  const int dparts = fsdf::hpart_parts(c->lm, n);
+  co.dparts = dparts ? dparts : 1;
+  const int grid = planned ? c->plan_grid : (int)((nc * co.dparts + 3) / 4);
+  HIPCHECK(c, fsdf::launch_planned_pass(c->precision, c->cull != 0, c->lm, P, d_pts, n, grid, out, co, c->stream,
+                                        pe ? (hipEvent_t)pe[0] : nullptr, pe ? (hipEvent_t)pe[1] : nullptr));
+  c->pass_kernel = fsdf::last_pass_kernel();
+  HIPCHECK(c, fsdf::launch_reduce_chunks(co, nc, c->lm.S, c->partials.get(), d_accum, c->stream,
+                                         pe ? (hipEvent_t)pe[2] : nullptr, skip));
+  if (!planned || ++c->plan_age >= kOrderEvery) {
+    int n4, n2;
+    plan_shape(c, nc, &n4, &n2);
+    const int64_t g = n4 + (n2 + 1) / 2 + (nc - n4 - n2 + 3) / 4;
+    if (c->plan.capacity() < (size_t)g * 4) HIPCHECK(c, hipStreamSynchronize(c->stream));
+    HIPCHECK(c, c->plan.reserve((size_t)g * 4));
+    HIPCHECK(c, fsdf::launch_plan(c->co.dur, nc, n4, n2, c->chunk.plan_order.get(), c->plan.get(), c->stream));
+    c->plan_grid = (int)g;
+    c->plan_nc = nc;
+    c->plan_age = 0;
+  }
+  return FSDF_OK;
+}
+
+// schedule: resident-cloud passes (repeated over the same cloud) launch their
+// workgroups heaviest-first by the previous pass's durations
+// posed / skip: the device solver loop's pass — its model posed by the
+// previous step (pose_model), its done flag
+static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, int64_t n, double* d_accum,
+                         int32_t* d_kstar, double* d_d, double* d_grad, const int32_t* d_perm, bool schedule,
+                         bool posed, const int* skip) {
+  if (c->lm.R > 0 && !c->rbf_ready)
+    return fail(c, FSDF_ERR_STATE, "eval: the scene has RBF surfaces: call fsdf_set_rbf_params first");
+  fsdf::PosedModel* P = nullptr;
+  int pbuf = 0;
+  int rc = pose_model(c, poses, &P, &pbuf, posed);
+  if (rc) return rc;
+  const bool resident = d_pts == c->cur.pts.get() && n == c->n;
+  const int nblocks = fsdf::pass_blocks(n, c->lm);
+  rc = ensure_partials(c, nblocks);
+  if (rc) return rc;
+  fsdf::PassOutputs out;
+  out.partials = c->partials.get();
+  out.kstar = d_kstar;
+  out.d = d_d;
+  out.grad = d_grad;
+  out.perm = d_perm;
+  out.stats = c->stats_on ? c->stats.get() : nullptr;
+  out.skip = skip;
+  out.chunk_ws = FSDF_CHUNK_WS && resident ? c->cur.chunk_ws.get() : nullptr;  // resident cloud only
+  // the previous pass's nearest surfaces as seeds (resident cloud, hull-only
+  // scenes of <= 64 surfaces; fsdf_internal.h PassOutputs::prior_in); marked
+  // written (prior_ok) once the pass is launched — stream-ordered, the next
+  // pass reads what this one writes
+  const bool prior = FSDF_PRIOR_SEEDS && resident && n > 0 && c->prior.capacity() >= (size_t)n && c->lm.R == 0 &&
+                     c->lm.S <= 64;
+  out.prior_out = prior ? c->prior.get() : nullptr;
+  out.prior_in = prior && c->prior_ok ? c->prior.get() : nullptr;
+  // planned window: (default min, model's default max], or (0, max_points] when set
+  const int64_t plan_max = c->plan_max_points >= 0 ? c->plan_max_points : fsdf::planned_default_max_points(c->lm);
+  const int64_t plan_min = c->plan_max_points >= 0 ? 0 : fsdf::planned_default_min_points();
+  if (schedule && n > plan_min && c->plan_enable && n <= plan_max && c->precision == 64 &&
+      fsdf::planned_pass(c->lm, n)) {
+    const bool prof = c->profiling && c->prof_used + 3 <= c->prof_ev.size();
+    const fsdf::Event* pe = prof ? &c->prof_ev[c->prof_used] : nullptr;
+    rc = run_planned(c, *P, d_pts, n, d_accum, out, pe, skip);
+    if (rc) return rc;
+    if (prior) c->prior_ok = true;
+    if (resident) c->last_pass_shape = 3;
+    if (prof) c->prof_used += 3;
+    return release_posed(c, pbuf);
+  }
+  const int ol = c->regrouped ? 1 : 0;  // (the layout's block order)
+  if (schedule && n > 0) {
+    HIPCHECK(c, c->block_cost.reserve(fsdf::kMaxBlocks));
+    HIPCHECK(c, c->block_order[0].reserve(fsdf::kMaxBlocks));
+    HIPCHECK(c, c->block_order[1].reserve(fsdf::kMaxBlocks));
+    out.cost = c->block_cost.get();
+    out.order = c->order_nblocks[ol] == nblocks ? c->block_order[ol].get() : nullptr;
+  }
+  if (n > 0) {
+    // profiling: the pass kernel's start / end and the reduce's end, stamped
+    // by the dispatches themselves (no packets of their own between kernels)
+    const bool prof = c->profiling && c->prof_used + 3 <= c->prof_ev.size();
+    const fsdf::Event* pe = prof ? &c->prof_ev[c->prof_used] : nullptr;
+    HIPCHECK(c, fsdf::launch_pass(c->precision, c->cull != 0, c->lm, *P, d_pts, n, nblocks, out, c->stream,
+                                  pe ? (hipEvent_t)pe[0] : nullptr, pe ? (hipEvent_t)pe[1] : nullptr));
+    c->pass_kernel = fsdf::last_pass_kernel();
+    if (prior) c->prior_ok = true;
+    if (resident) c->last_pass_shape = fsdf::hpart_pass(c->lm, n) ? 2 : 1;
+    rc = release_posed(c, pbuf);
+    if (rc) return rc;
+    if (prof) c->prof_used += 3;
+    // the order is rebuilt on the first scheduled pass of a grid and then every
+    // kOrderEvery passes (the heavy blocks of a cloud stay heavy from pass to
+    // pass; the rebuild is a ~7 us single-workgroup sort on the reduce launch)
+    const bool rebuild = out.cost && (c->order_nblocks[ol] != nblocks || ++c->order_age[ol] >= kOrderEvery);
+    HIPCHECK(c, fsdf::launch_reduce(c->partials.get(), nblocks, accum_len(c), d_accum, c->stream,
+                                    rebuild ? out.cost : nullptr, rebuild ? c->block_order[ol].get() : nullptr,
+                                    pe ? (hipEvent_t)pe[2] : nullptr, skip));
+    if (rebuild) {
+      c->order_nblocks[ol] = nblocks;
+      c->order_age[ol] = 0;
+    }
+  } else {
+    rc = release_posed(c, pbuf);
+    if (rc) return rc;
+    HIPCHECK(c, hipMemsetAsync(d_accum, 0, (size_t)accum_len(c) * sizeof(double), c->stream));
+  }
+  return FSDF_OK;
+}
+
+// A pass, then a prefetch still to be issued (fsdf_prefetch_points): its copy,
+// sort launches and their host-side cost go behind this pass, which the device
+// is already running (profiles/r06/prefetch_defer/). Its result waits for
+// fsdf_set_points_prefetched.
+int run_pass(fsdf_ctx* c, const double* poses, const void* d_pts, int64_t n, double* d_accum, int32_t* d_kstar,
+             double* d_d, double* d_grad, const int32_t* d_perm, bool schedule, bool posed, const int* skip) {
+  const int rc = run_pass_impl(c, poses, d_pts, n, d_accum, d_kstar, d_d, d_grad, d_perm, schedule, posed, skip);
+  if (!rc && c->prefetch_deferred) c->prefetch_rc = prefetch_issue(c);
+  return rc;
+}
+
+// per-point outputs of resident-cloud passes: scattered to caller order through
+// the sort permutation, or written in resident order (coalesced)
+// (a ranged cloud, fsdf_set_points_range: always resident order — its
+// permutation names indices of the WHOLE cloud, beyond the outputs' length)
+static const int32_t* out_perm(const fsdf_ctx* c) {
+  return c->out_order == FSDF_ORDER_RESIDENT || c->ranged ? nullptr : c->cur.perm.get();
+}
+
+static int get_perm(fsdf_ctx* c, int64_t* out, bool device) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->n > 0 && !out) return fail(c, FSDF_ERR_ARG, "get_permutation: null output");
+  HIPCHECK(c, hipSetDevice(c->device));
+  if (c->n == 0) return FSDF_OK;
+  if (const int32_t* d_perm = c->cur.perm.get()) {
+    std::vector<int32_t> p32;
+    if (device) {
+      HIPCHECK(c, fsdf::widen_permutation(d_perm, c->n, out, c->stream));
+    } else {
+      p32.resize((size_t)c->n);
+      HIPCHECK(c, hipMemcpyAsync(p32.data(), d_perm, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                 c->stream));
+    }
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < p32.size(); ++i) out[i] = p32[i];
+  } else if (device) {
+    std::vector<int64_t> id((size_t)c->n);
+    for (int64_t i = 0; i < c->n; ++i) id[(size_t)i] = i;
+    HIPCHECK(c, hipMemcpy(out, id.data(), (size_t)c->n * sizeof(int64_t), hipMemcpyHostToDevice));
+  } else {
+    for (int64_t i = 0; i < c->n; ++i) out[i] = i;
+  }
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_get_permutation(fsdf_ctx* c, int64_t* perm_out) { return get_perm(c, perm_out, false); }
+extern "C" int fsdf_get_permutation_device(fsdf_ctx* c, int64_t* d_perm_out) { return get_perm(c, d_perm_out, true); }
+
+extern "C" int fsdf_eval_device(fsdf_ctx* c, const double* poses, double* d_accum, int32_t* d_kstar, double* d_d,
+                                double* d_grad) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval: no model (call fsdf_set_model first)");
+  if (!poses || !d_accum) return fail(c, FSDF_ERR_ARG, "eval_device: poses and d_accum are required");
+  HIPCHECK(c, hipSetDevice(c->device));
+  return run_pass(c, poses, c->cur.pts.get(), c->n, d_accum, d_kstar, d_d, d_grad, out_perm(c), true);
+}
+
+int ensure_outputs(fsdf_ctx* c, int64_t n) {
+  HIPCHECK(c, c->kstar.reserve((size_t)n));
+  HIPCHECK(c, c->d.reserve((size_t)n));
+  HIPCHECK(c, c->grad.reserve((size_t)std::max<int64_t>(n, 1) * 3));
+  return FSDF_OK;
+}
+
+int ensure_host_acc(fsdf_ctx* c, int len) {
+  HIPCHECK(c, c->h_acc.reserve((size_t)len));
+  return FSDF_OK;
+}
+
+int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
+                 double* grad_out, bool want_pp) {
+  const int len = accum_len(c);
+  int rc = ensure_host_acc(c, len);
+  if (rc) return rc;
+  double* acc = c->h_acc.get();
+  HIPCHECK(c, hipMemcpyAsync(acc, c->model.accum.get(), len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (want_pp && n > 0) {
+    if (kstar_out)
+      HIPCHECK(c, hipMemcpyAsync(kstar_out, c->kstar.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (d_out) HIPCHECK(c, hipMemcpyAsync(d_out, c->d.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (grad_out)
+      HIPCHECK(c, hipMemcpyAsync(grad_out, c->grad.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  if (cost_out) *cost_out = acc[0];
+  if (accum_out) memcpy(accum_out, acc, len * sizeof(double));
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_eval(fsdf_ctx* c, const double* poses, double* cost_out, double* accum_out, int32_t* kstar_out,
+                         double* d_out, double* grad_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval: no model (call fsdf_set_model first)");
+  if (!poses) return fail(c, FSDF_ERR_ARG, "eval: poses required");
+  HIPCHECK(c, hipSetDevice(c->device));
+  const bool want_pp = kstar_out || d_out || grad_out;
+  if (want_pp) {
+    int rc = ensure_outputs(c, c->n);
+    if (rc) return rc;
+  }
+  int rc = run_pass(c, poses, c->cur.pts.get(), c->n, c->model.accum.get(), want_pp ? c->kstar.get() : nullptr,
+                    want_pp ? c->d.get() : nullptr, want_pp ? c->grad.get() : nullptr, out_perm(c), true);
+  if (rc) return rc;
+  return fetch(c, c->n, cost_out, accum_out, kstar_out, d_out, grad_out, want_pp);
+}

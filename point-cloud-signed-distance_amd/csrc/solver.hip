@@ -2,10 +2,10 @@
 // residual pass and its reduce, one launch turns
 // the accumulator into the next configuration, the next surface poses and the
 // next pass's posed model, so a whole frame of iterations is enqueued with no
-// host round trip (fsdf_descend, capi.hip descend_device; the default for
+// host round trip (fsdf_descend, iterate.hip descend_device; the default for
 // rigid scenes, fsdf_set_solver).
 //
-// Per iteration, the arithmetic of the host loop (capi.hip fsdf_descend around
+// Per iteration, the arithmetic of the host loop (iterate.hip fsdf_descend around
 // fsdf_value_and_gradient) in the same order, from kin_impl.h:
 //   chain rule  surface wrenches -> body sums (surfaces in index order) ->
 //               subtree sums (children in descending index, as the host's
@@ -28,11 +28,11 @@
 //   before the chain rule  per skin μ = M⁻¹λ from the pass's RBF accumulator
 //               block with the LU of the solve that produced the pass's rows,
 //               G_j (sum over i ascending), body wrenches in centre order,
-//               ∂c/∂δ = Rᵀ G + 2 weight δ, cost + weight Σδ² (capi.hip
+//               ∂c/∂δ = Rᵀ G + 2 weight δ, cost + weight Σδ² (iterate.hip
 //               iteration_finish); x, g, the divisors are [nq + 3 n_deform]
 //   after the FK  centres c_j = R_b (p_j + δ_j) + t_b, the fill, PA = LU, the
 //               weight solve, the next pass's RBF rows in the context
-//               precision (capi.hip iteration_prepare); centres, u, LU and
+//               precision (iterate.hip iteration_prepare); centres, u, LU and
 //               the row permutation go to the state slot for the next step
 // A singular / non-finite system ends the frame with error 3.
 //
@@ -47,7 +47,7 @@
 #include "rbf_impl.h"
 
 #ifndef FSDF_SOLVER_TIMES
-#define FSDF_SOLVER_TIMES 0  // diagnostic builds: per-phase clocks of the step (capi.hip prints them)
+#define FSDF_SOLVER_TIMES 0  // diagnostic builds: per-phase clocks of the step (iterate.hip prints them)
 #endif
 
 namespace fsdf {
@@ -431,7 +431,7 @@ __device__ void rbf_wave_solve(int m, const double* lu, const int32_t* prow, boo
 }
 
 // After the step's FK (L.R, L.t, L.x): the centres c_j = R_b (p_j + δ_j) + t_b
-// (capi.hip iteration_prepare's expression), every skin's fill, LU and weight
+// (iterate.hip iteration_prepare's expression), every skin's fill, LU and weight
 // solve: L.cen, L.lu (stored rows), L.prow, L.u. Ends with a barrier.
 template <int NT>
 __device__ void rbf_prepare(const SolverTree& T, const Lds& L, int* sing) {
@@ -470,7 +470,7 @@ __device__ void rbf_prepare(const SolverTree& T, const Lds& L, int* sing) {
 }
 
 // Before the chain rule: the adjoint of the last weight solve from the pass's
-// RBF accumulator block (capi.hip iteration_finish): per skin μ = M⁻¹λ (a
+// RBF accumulator block (iterate.hip iteration_finish): per skin μ = M⁻¹λ (a
 // wave), the pair factors 3 |c_j - c_i| (into the LU's place, done with), G_j
 // (a thread per (centre, component), i ascending), then the body wrenches in
 // centre order, skins in surface order (a thread per (body, component)) into

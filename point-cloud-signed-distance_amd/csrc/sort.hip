@@ -328,20 +328,6 @@ __global__ __launch_bounds__(kBlock) void widen_kernel(const int32_t* __restrict
   if (i < n) dst[i] = src[i];
 }
 
-template <typename P>
-hipError_t grow(P** p, size_t* cap, size_t need) {
-  if (*cap >= need && *p) return hipSuccess;
-  if (*p) {
-    hipError_t e = hipFree((void*)*p);
-    if (e != hipSuccess) return e;
-  }
-  *p = nullptr;
-  *cap = 0;
-  hipError_t e = hipMalloc((void**)p, need ? need : 1);
-  if (e == hipSuccess) *cap = need;
-  return e;
-}
-
 // Seed carry-over between frames (the new cloud's first pass seeded by the
 // nearest surface the previous cloud's last pass found nearby): a coarse
 // voxel grid over a box fixed per context; each previous point writes its k*
@@ -403,18 +389,6 @@ hipError_t vox_gather(int precision, const void* d_pts, int64_t n, const VoxBox&
   return hipGetLastError();
 }
 
-void free_sort_scratch(SortScratch& s) {
-  if (s.part) (void)hipFree(s.part);
-  if (s.k0) (void)hipFree(s.k0);
-  if (s.k1) (void)hipFree(s.k1);
-  if (s.i1) (void)hipFree(s.i1);
-  if (s.tmp) (void)hipFree(s.tmp);
-  if (s.pts) (void)hipFree(s.pts);
-  if (s.q0) (void)hipFree(s.q0);
-  if (s.q1) (void)hipFree(s.q1);
-  s = SortScratch();
-}
-
 hipError_t sort_points_spatial(const double* d_src, int64_t n, int precision, void* d_dst, int32_t* d_perm,
                               SortScratch& s, hipStream_t st) {
   if (n <= 0) return hipSuccess;
@@ -422,23 +396,23 @@ hipError_t sort_points_spatial(const double* d_src, int64_t n, int precision, vo
   const int nb = (int)std::min<int64_t>(kBoxBlocks, (n + kBlock - 1) / kBlock);
   const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
   hipError_t e;
-  if ((e = grow(&s.part, &s.part_cap, (size_t)(kBoxBlocks + 1) * 6 * sizeof(double))) != hipSuccess) return e;
-  if ((e = grow(&s.k0, &s.k_cap0, (size_t)n * sizeof(uint32_t))) != hipSuccess) return e;
-  if ((e = grow(&s.k1, &s.k_cap1, (size_t)n * sizeof(uint32_t))) != hipSuccess) return e;
-  if ((e = grow(&s.i1, &s.i_cap1, (size_t)n * sizeof(int32_t))) != hipSuccess) return e;
-  double* box = s.part + 6 * kBoxBlocks;
-  hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(kBlock), 0, st, d_src, n, s.part);
-  hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(kBlock), 0, st, s.part, nb, box);
+  if ((e = s.part.reserve((size_t)(kBoxBlocks + 1) * 6)) != hipSuccess) return e;
+  if ((e = s.k0.reserve((size_t)n)) != hipSuccess) return e;
+  if ((e = s.k1.reserve((size_t)n * sizeof(uint32_t))) != hipSuccess) return e;
+  if ((e = s.i1.reserve((size_t)n)) != hipSuccess) return e;
+  double* box = s.part.get() + 6 * kBoxBlocks;
+  hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(kBlock), 0, st, d_src, n, s.part.get());
+  hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(kBlock), 0, st, s.part.get(), nb, box);
   // keys and the identity index go to (k0, d_perm); sorted pairs end in the
   // double buffers' current halves
-  hipLaunchKernelGGL(curve_key_kernel, dim3(grid), dim3(kBlock), 0, st, d_src, n, box, s.k0, d_perm);
+  hipLaunchKernelGGL(curve_key_kernel, dim3(grid), dim3(kBlock), 0, st, d_src, n, box, s.k0.get(), d_perm);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  rocprim::double_buffer<uint32_t> keys(s.k0, s.k1);
-  rocprim::double_buffer<int32_t> vals(d_perm, s.i1);
+  rocprim::double_buffer<uint32_t> keys(s.k0.get(), (uint32_t*)s.k1.get());
+  rocprim::double_buffer<int32_t> vals(d_perm, s.i1.get());
   size_t need = 0;
   if ((e = rocprim::radix_sort_pairs(nullptr, need, keys, vals, (size_t)n, 0, 30, st)) != hipSuccess) return e;
-  if ((e = grow((char**)&s.tmp, &s.tmp_cap, need)) != hipSuccess) return e;
-  if ((e = rocprim::radix_sort_pairs(s.tmp, need, keys, vals, (size_t)n, 0, 30, st)) != hipSuccess) return e;
+  if ((e = s.tmp.reserve(need)) != hipSuccess) return e;
+  if ((e = rocprim::radix_sort_pairs(s.tmp.get(), need, keys, vals, (size_t)n, 0, 30, st)) != hipSuccess) return e;
   if (vals.current() != d_perm)
     if ((e = hipMemcpyAsync(d_perm, vals.current(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st)) !=
         hipSuccess)
@@ -452,13 +426,13 @@ hipError_t sort_points_spatial(const double* d_src, int64_t n, int precision, vo
 
 hipError_t cloud_box(const double* d_src, int64_t n, SortScratch& s, hipStream_t st, double** d_box) {
   hipError_t e;
-  if ((e = grow(&s.part, &s.part_cap, (size_t)(kBoxBlocks + 1) * 6 * sizeof(double))) != hipSuccess) return e;
-  double* box = s.part + 6 * kBoxBlocks;
+  if ((e = s.part.reserve((size_t)(kBoxBlocks + 1) * 6)) != hipSuccess) return e;
+  double* box = s.part.get() + 6 * kBoxBlocks;
   *d_box = box;
   if (n <= 0) return hipSuccess;  // (the slot only: curve_keys_device fills it from the host)
   const int nb = (int)std::min<int64_t>(kBoxBlocks, (n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(kBlock), 0, st, d_src, n, s.part);
-  hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(kBlock), 0, st, s.part, nb, box);
+  hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(kBlock), 0, st, d_src, n, s.part.get());
+  hipLaunchKernelGGL(bbox_final_kernel, dim3(1), dim3(kBlock), 0, st, s.part.get(), nb, box);
   return hipGetLastError();
 }
 
@@ -475,19 +449,19 @@ hipError_t sort_points_keyed(const double* d_src, const uint32_t* d_keys, const 
   if (n > INT32_MAX) return hipErrorInvalidValue;
   const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
   hipError_t e;
-  if ((e = grow(&s.q0, &s.q_cap0, (size_t)n * sizeof(uint64_t))) != hipSuccess) return e;
-  if ((e = grow(&s.q1, &s.q_cap1, (size_t)n * sizeof(uint64_t))) != hipSuccess) return e;
-  if ((e = grow(&s.i1, &s.i_cap1, (size_t)n * sizeof(int32_t))) != hipSuccess) return e;
-  if ((e = grow(&s.k0, &s.k_cap0, (size_t)n * sizeof(int32_t))) != hipSuccess) return e;
-  int32_t* pos0 = (int32_t*)s.k0;
-  hipLaunchKernelGGL(composite_key_kernel, dim3(grid), dim3(kBlock), 0, st, d_keys, d_index, n, s.q0, pos0);
+  if ((e = s.q0.reserve((size_t)n)) != hipSuccess) return e;
+  if ((e = s.q1.reserve((size_t)n)) != hipSuccess) return e;
+  if ((e = s.i1.reserve((size_t)n)) != hipSuccess) return e;
+  if ((e = s.k0.reserve((size_t)n)) != hipSuccess) return e;
+  int32_t* pos0 = (int32_t*)s.k0.get();
+  hipLaunchKernelGGL(composite_key_kernel, dim3(grid), dim3(kBlock), 0, st, d_keys, d_index, n, s.q0.get(), pos0);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  rocprim::double_buffer<uint64_t> keys(s.q0, s.q1);
-  rocprim::double_buffer<int32_t> vals(pos0, s.i1);
+  rocprim::double_buffer<uint64_t> keys(s.q0.get(), s.q1.get());
+  rocprim::double_buffer<int32_t> vals(pos0, s.i1.get());
   size_t need = 0;
   if ((e = rocprim::radix_sort_pairs(nullptr, need, keys, vals, (size_t)n, 0, 61, st)) != hipSuccess) return e;
-  if ((e = grow((char**)&s.tmp, &s.tmp_cap, need)) != hipSuccess) return e;
-  if ((e = rocprim::radix_sort_pairs(s.tmp, need, keys, vals, (size_t)n, 0, 61, st)) != hipSuccess) return e;
+  if ((e = s.tmp.reserve(need)) != hipSuccess) return e;
+  if ((e = rocprim::radix_sort_pairs(s.tmp.get(), need, keys, vals, (size_t)n, 0, 61, st)) != hipSuccess) return e;
   if (precision == 64)
     hipLaunchKernelGGL(gather_keyed_kernel<double>, dim3(grid), dim3(kBlock), 0, st, d_src, d_index, n, vals.current(),
                        (double*)d_dst, d_perm);
@@ -497,36 +471,31 @@ hipError_t sort_points_keyed(const double* d_src, const uint32_t* d_keys, const 
   return hipGetLastError();
 }
 
-hipError_t regroup_points(void** d_pts, int64_t* pts_cap, int64_t n, int precision, int32_t* d_perm, uint8_t* prior,
+hipError_t regroup_points(DevBuf<unsigned char>& pts, int64_t n, int precision, int32_t* d_perm, uint8_t* prior,
                           SortScratch& s, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   if (n > INT32_MAX) return hipErrorInvalidValue;
   const size_t tsz = precision == 64 ? sizeof(double) : sizeof(float);
   const int nwin = (int)((n + kRegroupWindow - 1) / kRegroupWindow);
   hipError_t e;
-  if ((e = grow((char**)&s.pts, &s.pts_cap, (size_t)n * 3 * tsz)) != hipSuccess) return e;
-  if ((e = grow(&s.k0, &s.k_cap0, (size_t)n * sizeof(uint32_t))) != hipSuccess) return e;  // the permutation
-  if ((e = grow(&s.k1, &s.k_cap1, (size_t)n)) != hipSuccess) return e;                     // the priors
-  if ((e = grow(&s.i1, &s.i_cap1, (size_t)64 * nwin * sizeof(int32_t))) != hipSuccess) return e;  // run starts
-  int32_t* perm2 = (int32_t*)s.k0;
-  uint8_t* prior2 = (uint8_t*)s.k1;
-  uint32_t* start = (uint32_t*)s.i1;
+  if ((e = s.pts.reserve((size_t)n * 3 * tsz)) != hipSuccess) return e;
+  if ((e = s.k0.reserve((size_t)n)) != hipSuccess) return e;  // the permutation
+  if ((e = s.k1.reserve((size_t)n)) != hipSuccess) return e;  // the priors
+  if ((e = s.i1.reserve((size_t)64 * nwin)) != hipSuccess) return e;  // run starts
+  int32_t* perm2 = (int32_t*)s.k0.get();
+  uint8_t* prior2 = s.k1.get();
+  uint32_t* start = (uint32_t*)s.i1.get();
   hipLaunchKernelGGL(regroup_count_kernel, dim3(nwin), dim3(kRegroupBlock), 0, st, prior, n, start, nwin);
   hipLaunchKernelGGL(regroup_scan_kernel, dim3(1), dim3(kRegroupScanBlock), 0, st, start, (int64_t)64 * nwin);
   if (precision == 64)
-    hipLaunchKernelGGL(regroup_scatter_kernel<double>, dim3(nwin), dim3(kRegroupBlock), 0, st, (const double*)*d_pts,
-                       d_perm, prior, n, start, nwin, (double*)s.pts, perm2, prior2);
+    hipLaunchKernelGGL(regroup_scatter_kernel<double>, dim3(nwin), dim3(kRegroupBlock), 0, st, (const double*)pts.get(),
+                       d_perm, prior, n, start, nwin, (double*)s.pts.get(), perm2, prior2);
   else
-    hipLaunchKernelGGL(regroup_scatter_kernel<float>, dim3(nwin), dim3(kRegroupBlock), 0, st, (const float*)*d_pts,
-                       d_perm, prior, n, start, nwin, (float*)s.pts, perm2, prior2);
+    hipLaunchKernelGGL(regroup_scatter_kernel<float>, dim3(nwin), dim3(kRegroupBlock), 0, st, (const float*)pts.get(),
+                       d_perm, prior, n, start, nwin, (float*)s.pts.get(), perm2, prior2);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // the regrouped cloud becomes the resident one (the old buffer the scratch)
-  void* old = *d_pts;
-  const int64_t old_cap = *pts_cap;
-  *d_pts = s.pts;
-  *pts_cap = (int64_t)(s.pts_cap / (3 * tsz));
-  s.pts = old;
-  s.pts_cap = (size_t)old_cap * 3 * tsz;
+  pts.swap(s.pts);
   if ((e = hipMemcpyAsync(d_perm, perm2, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st)) != hipSuccess)
     return e;
   return hipMemcpyAsync(prior, prior2, (size_t)n, hipMemcpyDeviceToDevice, st);

@@ -22,7 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "point-cloud-signed-distance_amd"))
 
-# the serial-equivalent rescale the kernel applies to split chunks (capi.hip run_planned:
+# the serial-equivalent rescale the kernel applies to split chunks (pass.hip run_planned:
 # scenes with >= 32 hulls, fewer); round 4's build used 5/2 and 8/5 for both
 RESCALE = {True: {4: 15 / 8, 2: 4 / 3}, False: {4: 5 / 2, 2: 8 / 5}}
 
@@ -44,7 +44,7 @@ def main():
     ctx.set_model([(s.hull.vertices, s.hull.faces, s.hull.planes) for s in m.surfaces])
     ctx.set_points(pts)
     nc = -(-len(pts) // 64)
-    # the round-4 default composition's counts (capi.hip kPlanDefault4 / 2, or the spare-slot rule),
+    # the round-4 default composition's counts (pass.hip kPlanDefault4 / 2, or the spare-slot rule),
     # as fixed shares: the split set is then the heaviest chunks, whatever the keyed plan would pick
     slots = 256 * 16
     n4 = min(nc, max(96, max(0, slots - nc) // 3))
