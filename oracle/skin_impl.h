@@ -7,7 +7,7 @@
  * TEST INFRASTRUCTURE ONLY (see flash_oracle.c's header).
  *
  * Each function mirrors the gfx950 kernel's template instantiation for the
- * same T (point-cloud-signed-distance_amd/csrc/sdf_kernels.hip, hull_sdf<T>,
+ * same T (point-cloud-signed-distance_amd/csrc/sdf_kernels.hip and its headers, hull_sdf<T>,
  * cert_step<T>, closest_on_triangle<T>, rbf_field<T>): the world planes and
  * vertices are computed in fp64 from the fp64 poses and rounded once to R
  * (pose_body<T>), everything after that runs in R with explicit fma,

@@ -31,12 +31,9 @@ static void free_model(fsdf_ctx* c) {
   }
   c->rbf_slot = 0;
   c->rbf_ready = false;
-  if (c->pose_stream) (void)hipStreamSynchronize(c->pose_stream);
-  c->posed[0] = PosedBuffers();
-  c->posed[1] = PosedBuffers();
+  c->posed = PosedBuffers();
   c->rbf32.reset();
-  c->pm = c->pm_alt = fsdf::PosedModel();
-  c->pm_next = 0;
+  c->pm = fsdf::PosedModel();
   // (the partition tiers are a context setting: they survive a model change)
   const int64_t h4 = c->lm.hpart4_points, h2 = c->lm.hpart2_points;
   c->plan_nc = -1;
@@ -67,16 +64,9 @@ extern "C" int fsdf_create(fsdf_ctx** out, const fsdf_opts* opts) {
   // the prefetch copy stream right after the context stream: HIP hands out its
   // hardware queues round robin by stream creation, so the two land on
   // different queues (on a shared one the copy would serialise with the passes)
-  // (the pose stream only where the pose overlap is built in: every stream of a
-  // process shares its few hardware queues — GPU_MAX_HW_QUEUES, 4 by default —
-  // and a stream sharing the context stream's queue serialises with it)
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || c->device < 0 || c->device >= ndev ||
       hipSetDevice(c->device) != hipSuccess || c->own_stream.create() != hipSuccess ||
-      c->copy_stream.create() != hipSuccess || c->ev_prefetch.create(hipEventDisableTiming) != hipSuccess ||
-      (FSDF_POSE_OVERLAP && c->pose_stream.create() != hipSuccess) ||
-      c->ev_pose.create(hipEventDisableTiming) != hipSuccess ||
-      c->ev_pm_free[0].create(hipEventDisableTiming) != hipSuccess ||
-      c->ev_pm_free[1].create(hipEventDisableTiming) != hipSuccess) {
+      c->copy_stream.create() != hipSuccess || c->ev_prefetch.create(hipEventDisableTiming) != hipSuccess) {
     delete c;
     return FSDF_ERR_HIP;
   }
@@ -89,7 +79,6 @@ extern "C" int fsdf_destroy(fsdf_ctx* c) {
   if (!c) return FSDF_ERR_ARG;
   (void)hipSetDevice(c->device);  // (before anything is freed: contexts of several devices share a process)
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->pose_stream) (void)hipStreamSynchronize(c->pose_stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   delete c;
   return FSDF_OK;
@@ -275,7 +264,7 @@ extern "C" int fsdf_set_surfaces(fsdf_ctx* c, const fsdf_surface* surfs, int32_t
       // pairs, 32 B per two faces) and vertex rows of 4 T, one 16-byte face row
       // per face (M64 f64: 4864 B; 4 waves + the wrench rows + the hull table
       // stay under 40 KiB, i.e. 4 workgroups per CU)
-      const int plane_bytes = (tsz_ == 8 && FSDF_SCREEN32) ? 32 * ((h.n_faces + 1) / 2) : h.n_faces * 4 * tsz_;
+      const int plane_bytes = tsz_ == 8 ? 32 * ((h.n_faces + 1) / 2) : h.n_faces * 4 * tsz_;
       stage_bytes = std::max(stage_bytes, plane_bytes + h.n_vertices * 4 * tsz_ + 16 * h.n_faces);
       // (+ the fp64 planes, 32 B per face, when they are staged too; the
       // stage is then a copy of the hull's stage image, whose pair region is
@@ -289,7 +278,7 @@ extern "C" int fsdf_set_surfaces(fsdf_ctx* c, const fsdf_surface* surfs, int32_t
   // at least; the resident-order gradient store transposes 64 x 3 doubles in it
   auto finish_stage = [&](int b) {
     b = (std::max(b, 64 * 4 * std::max(tsz_, 8)) + 15) & ~15;
-    if (FSDF_RED_IN_STAGE && S <= 64 && rbf_surface.empty())
+    if (S <= 64 && rbf_surface.empty())
       b = std::max(b, fsdf::kRedInStageMinBytes);  // wrench rows + transpose after the evaluation
     return b;
   };
@@ -299,7 +288,7 @@ extern "C" int fsdf_set_surfaces(fsdf_ctx* c, const fsdf_surface* surfs, int32_t
   // one-chunk-per-wave pass (wrench rows in the stage) then still runs 4
   // workgroups per CU
   int planes64 = 0;
-  if (FSDF_STAGE_PLANES64 && tsz_ == 8 && FSDF_SCREEN32 && FSDF_RED_IN_STAGE && S <= 64 && rbf_surface.empty()) {
+  if (tsz_ == 8 && S <= 64 && rbf_surface.empty()) {
     fsdf::LocalModel probe;
     probe.K = K;
     probe.S = S;
@@ -368,16 +357,15 @@ extern "C" int fsdf_set_surfaces(fsdf_ctx* c, const fsdf_surface* surfs, int32_t
     memcpy(img.data() + 4 * base, face_rows.data() + 4 * (size_t)face_off[h], (size_t)nf * 4 * sizeof(int32_t));
   }
   auto room = [](auto& buf, size_t n) { return n ? buf.reserve(n) : hipSuccess; };  // (an empty array: no buffer)
-  for (PosedBuffers& pb : c->posed) {
-    HIPCHECK(c, room(pb.verts_w, (size_t)V * 4 * tsz));
-    HIPCHECK(c, room(pb.hscale_w, (size_t)K * tsz));
-    HIPCHECK(c, pb.planes_w.reserve((size_t)std::max(F, 1) * 4 * tsz));
-    HIPCHECK(c, room(pb.spheres_w, (size_t)K * fsdf::kBoundFloats));
-    HIPCHECK(c, pb.screen_w.reserve((size_t)std::max(F + K, 1) * 4));
-    if (planes64) {
-      HIPCHECK(c, pb.image_w.reserve(chunks * 16));
-      HIPCHECK(c, hipMemcpy(pb.image_w.get(), img.data(), chunks * 16, hipMemcpyHostToDevice));
-    }
+  PosedBuffers& pb = c->posed;
+  HIPCHECK(c, room(pb.verts_w, (size_t)V * 4 * tsz));
+  HIPCHECK(c, room(pb.hscale_w, (size_t)K * tsz));
+  HIPCHECK(c, pb.planes_w.reserve((size_t)std::max(F, 1) * 4 * tsz));
+  HIPCHECK(c, room(pb.spheres_w, (size_t)K * fsdf::kBoundFloats));
+  HIPCHECK(c, pb.screen_w.reserve((size_t)std::max(F + K, 1) * 4));
+  if (planes64) {
+    HIPCHECK(c, pb.image_w.reserve(chunks * 16));
+    HIPCHECK(c, hipMemcpy(pb.image_w.get(), img.data(), chunks * 16, hipMemcpyHostToDevice));
   }
   if (R > 0) {
     HIPCHECK(c, mb.rbf64.reserve((size_t)nrows * 4));
@@ -419,18 +407,14 @@ extern "C" int fsdf_set_surfaces(fsdf_ctx* c, const fsdf_surface* surfs, int32_t
   lm.rbf_surface = mb.rbf_surface.get();
   lm.rbf_row_off = mb.rbf_row_off.get();
   lm.rbf_acc_off = mb.rbf_acc_off.get();
-  fsdf::PosedModel* views[2] = {&c->pm, &c->pm_alt};
-  for (int b = 0; b < 2; ++b) {
-    const PosedBuffers& pb = c->posed[b];
-    views[b]->planes_w = pb.planes_w.get();
-    views[b]->spheres_w = pb.spheres_w.get();
-    views[b]->verts_w = pb.verts_w.get();
-    views[b]->hscale_w = pb.hscale_w.get();
-    views[b]->screen_w = pb.screen_w.get();
-    views[b]->image_w = pb.image_w.get();
-    // per-pass RBF rows: one buffer for both, context-stream ordered (f64 contexts read the f64 rows)
-    views[b]->rbf_rows = c->precision == 64 ? (void*)mb.rbf64.get() : (void*)c->rbf32.get();
-  }
+  c->pm.planes_w = pb.planes_w.get();
+  c->pm.spheres_w = pb.spheres_w.get();
+  c->pm.verts_w = pb.verts_w.get();
+  c->pm.hscale_w = pb.hscale_w.get();
+  c->pm.screen_w = pb.screen_w.get();
+  c->pm.image_w = pb.image_w.get();
+  // per-pass RBF rows (f64 contexts read the f64 rows)
+  c->pm.rbf_rows = c->precision == 64 ? (void*)mb.rbf64.get() : (void*)c->rbf32.get();
   c->h_surface_kind = surface_kind;
   c->h_n_centers.assign(S, 0);
   for (int k = 0; k < S; ++k) c->h_n_centers[k] = surfs[k].kind == FSDF_SURFACE_RBF ? surfs[k].n_centers : 0;
@@ -609,10 +593,6 @@ extern "C" int fsdf_pass_time(fsdf_ctx* c, double* total_ms, int64_t* launches) 
   return fsdf_pass_times(c, &k, total_ms, launches);
 }
 
-
-#ifndef FSDF_WAVE_TIMES
-#define FSDF_WAVE_TIMES 0
-#endif
 // 24 counters; diagnostic builds with -DFSDF_WAVE_TIMES=1 append per-wave clocks
 static constexpr int kStatCount = FSDF_WAVE_TIMES ? 32 + 32 * fsdf::kMaxBlocks : 24;
 
@@ -647,14 +627,10 @@ extern "C" int fsdf_raycast(fsdf_ctx* c, const double* poses, const double* orig
   if (c->q64.capacity() < (size_t)n * 3) HIPCHECK(c, hipStreamSynchronize(c->stream));
   HIPCHECK(c, c->q64.reserve((size_t)n * 3));
   HIPCHECK(c, hipMemcpyAsync(c->q64.get(), rays, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  fsdf::PosedModel* P = nullptr;
-  int pbuf = 0;
-  rc = pose_model(c, poses, &P, &pbuf);
+  rc = pose_model(c, poses);
   if (rc) return rc;
-  HIPCHECK(c, fsdf::launch_raycast(c->precision, c->cull != 0, c->lm, *P, origin, c->q64.get(), n, c->d.get(),
+  HIPCHECK(c, fsdf::launch_raycast(c->precision, c->cull != 0, c->lm, c->pm, origin, c->q64.get(), n, c->d.get(),
                                    c->stream));
-  rc = release_posed(c, pbuf);
-  if (rc) return rc;
   HIPCHECK(c, hipMemcpyAsync(depth_out, c->d.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHECK(c, hipStreamSynchronize(c->stream));
   return FSDF_OK;

@@ -34,7 +34,7 @@ static int finish_resident(fsdf_ctx* c, int64_t n, bool ranged, bool spheres_don
 // a quarter of its extent each way, fixed for the context. Seeds only order
 // the search — the pass's bits do not depend on them (tests/test_gpu_tracking.py).
 static bool seeds_apply(const fsdf_ctx* c) {
-  return FSDF_PRIOR_SEEDS && c->sort_points && c->lm.R == 0 && c->lm.S <= 64 && c->lm.K > 0;
+  return c->sort_points && c->lm.R == 0 && c->lm.S <= 64 && c->lm.K > 0;
 }
 
 static int ensure_vox_box(fsdf_ctx* c, const double* d_src, int64_t n) {

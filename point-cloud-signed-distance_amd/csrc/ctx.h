@@ -19,25 +19,6 @@
 #include "flashsdf.h"
 #include "fsdf_internal.h"
 
-#ifndef FSDF_POSE_OVERLAP
-#define FSDF_POSE_OVERLAP 0  // (pose_model: measured slower, off)
-#endif
-#ifndef FSDF_PRIOR_SEEDS
-#define FSDF_PRIOR_SEEDS 1
-#endif
-#ifndef FSDF_ORDER_EVERY
-#define FSDF_ORDER_EVERY 16
-#endif
-#ifndef FSDF_CHUNK_WS
-#define FSDF_CHUNK_WS 1  // passes over the resident cloud read the chunk spheres of set_points
-#endif
-// fsdf_value_and_gradient: the reduction kernel stores the accumulator into
-// the pinned host buffer itself (no D2H copy command before the sync). Same
-// results; full iteration -1.5 to -2.5 us against the pinned copy
-// (profiles/r02/experiments/r02zc).
-#ifndef FSDF_ZERO_COPY_ACCUM
-#define FSDF_ZERO_COPY_ACCUM 1
-#endif
 constexpr int kOrderEvery = FSDF_ORDER_EVERY;
 constexpr int kPoseRing = 8;
 
@@ -83,8 +64,8 @@ struct fsdf_ctx {
   // streams and events ahead of the buffers: destroyed after them
   fsdf::Stream own_stream;
   hipStream_t stream = nullptr;  // own_stream or the caller's (fsdf_set_stream)
-  fsdf::Stream pose_stream, copy_stream;
-  fsdf::Event ev_pose, ev_pm_free[2], ev_prefetch;
+  fsdf::Stream copy_stream;
+  fsdf::Event ev_prefetch;
   fsdf::Event pose_ev[kPoseRing], rbf_ev[kPoseRing];
   std::vector<fsdf::Event> prof_ev;  // pass-kernel timing (fsdf_profile_pass): triples
   std::string err;
@@ -99,13 +80,11 @@ struct fsdf_ctx {
   std::vector<int32_t> h_surface_kind, h_n_centers;  // host copy of the surface list (set_surfaces)
   int rbf_slot = 0;
   bool rbf_ready = false;
-  // posed model, double-buffered: pass i poses into buffer i % 2 on its own
-  // stream while the context stream still runs pass i-1 / its reduce
-  // (FSDF_POSE_OVERLAP); ev_pm_free[b] marks the last read of buffer b
-  fsdf::PosedModel pm, pm_alt;
-  PosedBuffers posed[2];
-  fsdf::DevBuf<float> rbf32;  // the per-pass RBF rows of f32 contexts (both posed models' rbf_rows)
-  int pm_next = 0;
+  // posed model: rewritten by every pass's pose kernel (pose_model) or by the
+  // device solver's step, in order on the context stream
+  fsdf::PosedModel pm;
+  PosedBuffers posed;
+  fsdf::DevBuf<float> rbf32;  // the per-pass RBF rows of f32 contexts (pm.rbf_rows)
   // poses: pinned ring + device copy (model.poses)
   fsdf::PinnedBuf<double> h_poses[kPoseRing];
   int pose_slot = 0;
@@ -185,7 +164,7 @@ struct fsdf_ctx {
     int nb = 0, nq = 0;
     std::vector<int32_t> parent, kind, qoff, surface_body;
     std::vector<double> axis, AR, At, BR, Bt, frame_R, frame_t;
-    std::vector<double> R, t, Rb, tb, poses, accum, work;  // scratch
+    std::vector<double> R, t, Rb, tb, poses, work;  // scratch
     // RBF surfaces (fsdf_set_rbf_centres), in surface order; n == 0: undeclared
     struct Rbf {
       int n_sp = 0, n = 0;
@@ -242,8 +221,7 @@ static inline size_t point_bytes(const fsdf_ctx* c) { return c->precision == 64 
 int adopt_points_device(fsdf_ctx* c, const double* d_src, int64_t n, fsdf::DevBuf<unsigned char>& dst);
 int prefetch_issue(fsdf_ctx* c);
 // pass.hip
-int pose_model(fsdf_ctx* c, const double* poses, fsdf::PosedModel** out, int* buf, bool posed = false);
-int release_posed(fsdf_ctx* c, int buf);
+int pose_model(fsdf_ctx* c, const double* poses, bool posed = false);
 int run_pass(fsdf_ctx* c, const double* poses, const void* d_pts, int64_t n, double* d_accum, int32_t* d_kstar,
              double* d_d, double* d_grad, const int32_t* d_perm, bool schedule, bool posed = false,
              const int* skip = nullptr);

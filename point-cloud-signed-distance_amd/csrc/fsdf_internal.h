@@ -36,38 +36,49 @@
 
 #include "device_buffers.h"
 
+// Every -DFSDF_... build switch of the library, with its default: four
+// diagnostics (0 / 1), then the tunables. `make dev EXTRA=-D...` sets them
+// (Makefile, tools/); the shipped library is the defaults. Test them with #if.
+#ifndef FSDF_WAVE_TIMES
+#define FSDF_WAVE_TIMES 0    // per-wave timeline with per-phase clocks in fsdf_kernel_stats (tools/wave_times.py)
+#endif
+#ifndef FSDF_HOST_TIMES
+#define FSDF_HOST_TIMES 0    // host clocks of the solver loops, printed by fsdf_descend (tools/host_gap_probe.py)
+#endif
+#ifndef FSDF_SOLVER_TIMES
+#define FSDF_SOLVER_TIMES 0  // per-phase clocks of the device solver step, printed by fsdf_descend
+#endif
+#ifndef FSDF_BENCH_ONLY
+#define FSDF_BENCH_ONLY 0    // instantiate only the bench variant of the pass kernel (make dev sets it)
+#endif
+#ifndef FSDF_PLANE_BATCH
+#define FSDF_PLANE_BATCH 8   // plane rows per LDS batch of the plane max (power of 2, >= 2)
+#endif
+#ifndef FSDF_SCREEN_ILP
+#define FSDF_SCREEN_ILP 4    // independent 8-face batches per iteration of the fp32 screen
+#endif
+#ifndef FSDF_PASS_WAVES_PER_SIMD
+#define FSDF_PASS_WAVES_PER_SIMD 4  // the pass kernels' occupancy target (VGPR budget 512 / w)
+#endif
+#ifndef FSDF_ORDER_EVERY
+#define FSDF_ORDER_EVERY 16  // passes between rebuilds of the block order / the plan
+#endif
+#ifndef FSDF_MAX_BLOCKS
+#define FSDF_MAX_BLOCKS 16384  // pass grid cap (grid-stride beyond)
+#endif
+
 namespace fsdf {
 
-// fp32-screened plane max in f64 contexts (sdf_kernels.hip screen_plane_max);
-// it also fixes the f64 LDS stage layout (screening pairs instead of planes),
-// so fsdf_set_surfaces sizes the stage from the same switch.
-#ifndef FSDF_SCREEN32
-#define FSDF_SCREEN32 1
-#endif
-// f64 contexts stage the fp64 planes too (fix-up, max face, certificates read
-// LDS instead of L1/L2); sizes the stage in fsdf_set_surfaces
-// Wrench rows in the wave's stage for one-chunk-per-wave passes (pass_kernel
-// ALIAS); the stage is then at least the rows + the gradient transpose.
-#ifndef FSDF_RED_IN_STAGE
-#define FSDF_RED_IN_STAGE 1
-#endif
+// one-chunk-per-wave passes (pass_kernel ALIAS) keep the wrench rows in the
+// wave's stage: the stage is then at least the rows + the gradient transpose
 constexpr int kRedInStageMinBytes = (64 * 6 + 2) * 8 + 64 * 3 * 8;
-#ifndef FSDF_STAGE_PLANES64
-#define FSDF_STAGE_PLANES64 1
-#endif
 
 constexpr int kBlock = 256;
-#ifndef FSDF_PASS_BLOCK
-#define FSDF_PASS_BLOCK 256
-#endif
-constexpr int kPassBlock = FSDF_PASS_BLOCK;  // pass-kernel workgroup (64 or a multiple)
-constexpr int kBoundFloats = 20;   // spheres_w row (sphere + oriented box)        // 4 waves of 64
+constexpr int kPassBlock = 256;    // pass-kernel workgroup: 4 waves of 64
+constexpr int kBoundFloats = 20;   // spheres_w row (sphere + oriented box)
 constexpr int kLdsPerCu = 163840;  // gfx950 LDS per CU
 constexpr int kMaxLds = 163840;    // LDS a workgroup may declare (gfx950)
 constexpr int kMaxHulls = 256;     // 4 accumulator slots per lane
-#ifndef FSDF_MAX_BLOCKS
-#define FSDF_MAX_BLOCKS 16384
-#endif
 constexpr int kMaxBlocks = FSDF_MAX_BLOCKS;  // pass grid cap (grid-stride beyond)
 constexpr int kMaxRbfAccum = 512;  // Σ (4n+4) over RBF skins (= kMaxRbfAcc in the kernel)
 
@@ -95,7 +106,7 @@ struct LocalModel {
   // face_off[hull], vert_off[hull] — one 16-B load instead of a chain of them
   const int32_t* item_meta = nullptr;
   int stage_bytes = 0;                 // per-wave LDS stage, context precision (multiple of 16)
-  int planes64 = 0;                    // f64: stage the fp64 planes too (FSDF_STAGE_PLANES64, if they fit)
+  int planes64 = 0;                    // f64: stage the fp64 planes too (if they fit: fsdf_set_surfaces)
   // hull-partitioned pass tiers (pass_kernel HPART, hpart_parts): clouds of
   // up to hpart4_points run 4 waves per chunk, up to hpart2_points 2; -1 =
   // the model's default (hpart_default_limits), 0 = tier off (fsdf_set_partition)
@@ -127,7 +138,7 @@ struct PosedModel {
 };
 
 struct PassOutputs {
-  double* partials = nullptr;  // line tiles (sdf_kernels.hip pidx)
+  double* partials = nullptr;  // line tiles (pass_kernels.h pidx)
   int32_t* kstar = nullptr;    // optional, caller order
   double* d = nullptr;         // optional
   double* grad = nullptr;      // optional [n][3]
@@ -153,7 +164,7 @@ struct PassOutputs {
   const int* skip = nullptr;
 };
 
-// Planned pass (sdf_kernels.hip planned_pass_kernel): per-chunk partial rows
+// Planned pass (pass_kernels.h planned_pass_kernel): per-chunk partial rows
 // of a resident cloud (nc = ceil(n/64) chunks) and the workgroup plan.
 struct ChunkOutputs {
   int32_t* hdr = nullptr;      // [nc][4] surfaces of entries 0..3 (-1: none); [c][0] == -2: dense row

@@ -269,8 +269,9 @@ extern "C" int fsdf_value_and_gradient(fsdf_ctx* c, const double* x, double* cos
   int rc = iteration_prepare(c, x, "value_and_gradient");
   if (rc) return rc;
   auto& M = c->mech;
-#if FSDF_ZERO_COPY_ACCUM
-  // the reduction stores the accumulator straight into pinned host memory
+  // the reduction stores the accumulator straight into pinned host memory (no
+  // D2H copy command before the sync: the full iteration is 1.5 to 2.5 us
+  // faster than with the pinned copy, profiles/r02/experiments/r02zc)
   rc = ensure_host_acc(c, accum_len(c));
   if (rc) return rc;
   double* d_acc_host = nullptr;
@@ -293,17 +294,6 @@ extern "C" int fsdf_value_and_gradient(fsdf_ctx* c, const double* x, double* cos
   ++g_host_n;
 #endif
   return rc;
-#else
-  rc = run_pass(c, M.poses.data(), c->cur.pts.get(), c->n, c->model.accum.get(), nullptr, nullptr, nullptr, nullptr,
-                true);
-  if (rc) return rc;
-  rc = iteration_regroup(c);
-  if (rc) return rc;
-  M.accum.resize(accum_len(c));
-  rc = fetch(c, c->n, nullptr, M.accum.data(), nullptr, nullptr, nullptr, false);
-  if (rc) return rc;
-  return iteration_finish(c, x, M.accum.data(), cost_out, grad_out, "value_and_gradient");
-#endif
 }
 
 // The solver loop of estimate_state (src/tracking.jl:16-26 with the
@@ -508,9 +498,8 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
   st.weight = M.weight;
   st.limit = iteration_limit;
   HIPCHECK(c, hipMemsetAsync(st.flags, 0, 4 * sizeof(int), c->stream));
-  // (the init and every step pose the next pass's model themselves: the
-  // passes below launch no pose kernel; FSDF_POSE_OVERLAP is off, c->pm is
-  // the one posed model)
+  // (the init and every step pose the next pass's model, c->pm, themselves:
+  // the passes below launch no pose kernel)
   HIPCHECK(c, fsdf::launch_solver_init(c->stree, st, c->lm, c->pm, c->precision, c->stream));
   // (the init wrote the first pass's RBF rows; as it was again on every return but a frame's good end)
   struct RbfReady {
@@ -545,7 +534,7 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
 #endif
   int flags[4];
   memcpy(flags, h + 3 * nx + 1, sizeof flags);
-#ifdef FSDF_SOLVER_TIMES
+#if FSDF_SOLVER_TIMES
   {
     unsigned long long tt[16];
     fsdf::solver_times(tt);
@@ -589,7 +578,6 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
   // (fsdf_set_solver), their skins' LU factors and work arrays counted. A
   // scene whose skins are not all declared, or name a deformation row that
   // does not exist, takes the host loop, which reports it.
-  // (the step poses c->pm itself: not with the double-buffered pose overlap)
   const bool rigid = c->lm.R == 0 && Mc.n_deform == 0;
   const bool required = c->solver_device == 2 || c->solver_device == 4;
   bool declared = (int)Mc.rbf.size() == c->lm.R || c->lm.R == 0;
@@ -598,7 +586,7 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
     for (int j = 0; j < D.n; ++j) declared = declared && D.drow[j] < Mc.n_deform;
   }
   bool device_loop = c->solver_device && iteration_limit > 0 && (rigid || (c->solver_device >= 3 && declared)) &&
-                     c->n > 0 && !FSDF_POSE_OVERLAP;
+                     c->n > 0;
   if (device_loop && !c->solver_tree_ok) {
     HIPCHECK(c, hipSetDevice(c->device));
     const int rc = build_solver_tree(c);

@@ -36,43 +36,20 @@ static int upload_poses(fsdf_ctx* c, const double* poses, hipStream_t st) {
   return FSDF_OK;
 }
 
-// Pose the model for one pass into the next posed buffer. With
-// FSDF_POSE_OVERLAP the upload and pose kernel run on the context's pose
-// stream — behind the last reader of that buffer (two passes back), ahead of
-// the current pass's kernels on the context stream, which waits for them — so
-// the pose kernel overlaps the previous pass's tail and reduce. *buf: the
-// buffer index to release with release_posed() after its last reader.
-// Measured: the cross-stream event waits cost more than the overlap saves
-// (+10 us per step on M64), so it is off and the pose kernel runs in order.
+// Pose the model for one pass into c->pm, in order on the context stream.
+// (Posing into a second buffer on a stream of its own, to overlap the previous
+// pass's tail and reduce, measured slower: the cross-stream event waits cost
+// more than the overlap saves, +10 us per step on M64.)
 // posed: the model is already posed on the device (the device solver loop's
 // step poses the next pass's model itself, solver.hip): no pose launch.
-int pose_model(fsdf_ctx* c, const double* poses, fsdf::PosedModel** out, int* buf, bool posed) {
-  const int b = FSDF_POSE_OVERLAP ? c->pm_next : 0;
-  c->pm_next ^= FSDF_POSE_OVERLAP ? 1 : 0;
-  fsdf::PosedModel* P = b ? &c->pm_alt : &c->pm;
-  P->rbf_rows = c->pm.rbf_rows;  // per-pass RBF rows: one buffer, context-stream ordered
-  const hipStream_t ps = FSDF_POSE_OVERLAP ? c->pose_stream : c->stream;
-  if (FSDF_POSE_OVERLAP) HIPCHECK(c, hipStreamWaitEvent(ps, c->ev_pm_free[b], 0));
-  if (!posed) {
-    int rc = upload_poses(c, poses, ps);
-    if (rc) return rc;
-    HIPCHECK(c, fsdf::launch_pose(c->precision, c->lm, c->model.poses.get(), *P, ps,
-                                  c->lm.S <= fsdf::kPoseArgMax ? poses : nullptr));
-  }
-  if (FSDF_POSE_OVERLAP) {
-    HIPCHECK(c, hipEventRecord(c->ev_pose, ps));
-    HIPCHECK(c, hipStreamWaitEvent(c->stream, c->ev_pose, 0));
-  }
-  *out = P;
-  *buf = b;
+int pose_model(fsdf_ctx* c, const double* poses, bool posed) {
+  if (posed) return FSDF_OK;
+  int rc = upload_poses(c, poses, c->stream);
+  if (rc) return rc;
+  HIPCHECK(c, fsdf::launch_pose(c->precision, c->lm, c->model.poses.get(), c->pm, c->stream,
+                                c->lm.S <= fsdf::kPoseArgMax ? poses : nullptr));
   return FSDF_OK;
 }
-
-int release_posed(fsdf_ctx* c, int buf) {
-  if (FSDF_POSE_OVERLAP) HIPCHECK(c, hipEventRecord(c->ev_pm_free[buf], c->stream));
-  return FSDF_OK;
-}
-
 
 static int ensure_chunk_outputs(fsdf_ctx* c, int64_t nc) {
   if (c->co.cap >= nc && c->co_s >= c->lm.S) return FSDF_OK;
@@ -180,9 +157,7 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
                          bool posed, const int* skip) {
   if (c->lm.R > 0 && !c->rbf_ready)
     return fail(c, FSDF_ERR_STATE, "eval: the scene has RBF surfaces: call fsdf_set_rbf_params first");
-  fsdf::PosedModel* P = nullptr;
-  int pbuf = 0;
-  int rc = pose_model(c, poses, &P, &pbuf, posed);
+  int rc = pose_model(c, poses, posed);
   if (rc) return rc;
   const bool resident = d_pts == c->cur.pts.get() && n == c->n;
   const int nblocks = fsdf::pass_blocks(n, c->lm);
@@ -196,13 +171,12 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
   out.perm = d_perm;
   out.stats = c->stats_on ? c->stats.get() : nullptr;
   out.skip = skip;
-  out.chunk_ws = FSDF_CHUNK_WS && resident ? c->cur.chunk_ws.get() : nullptr;  // resident cloud only
+  out.chunk_ws = resident ? c->cur.chunk_ws.get() : nullptr;  // resident cloud only
   // the previous pass's nearest surfaces as seeds (resident cloud, hull-only
   // scenes of <= 64 surfaces; fsdf_internal.h PassOutputs::prior_in); marked
   // written (prior_ok) once the pass is launched — stream-ordered, the next
   // pass reads what this one writes
-  const bool prior = FSDF_PRIOR_SEEDS && resident && n > 0 && c->prior.capacity() >= (size_t)n && c->lm.R == 0 &&
-                     c->lm.S <= 64;
+  const bool prior = resident && n > 0 && c->prior.capacity() >= (size_t)n && c->lm.R == 0 && c->lm.S <= 64;
   out.prior_out = prior ? c->prior.get() : nullptr;
   out.prior_in = prior && c->prior_ok ? c->prior.get() : nullptr;
   // planned window: (default min, model's default max], or (0, max_points] when set
@@ -212,12 +186,12 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
       fsdf::planned_pass(c->lm, n)) {
     const bool prof = c->profiling && c->prof_used + 3 <= c->prof_ev.size();
     const fsdf::Event* pe = prof ? &c->prof_ev[c->prof_used] : nullptr;
-    rc = run_planned(c, *P, d_pts, n, d_accum, out, pe, skip);
+    rc = run_planned(c, c->pm, d_pts, n, d_accum, out, pe, skip);
     if (rc) return rc;
     if (prior) c->prior_ok = true;
     if (resident) c->last_pass_shape = 3;
     if (prof) c->prof_used += 3;
-    return release_posed(c, pbuf);
+    return FSDF_OK;
   }
   const int ol = c->regrouped ? 1 : 0;  // (the layout's block order)
   if (schedule && n > 0) {
@@ -232,13 +206,11 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
     // by the dispatches themselves (no packets of their own between kernels)
     const bool prof = c->profiling && c->prof_used + 3 <= c->prof_ev.size();
     const fsdf::Event* pe = prof ? &c->prof_ev[c->prof_used] : nullptr;
-    HIPCHECK(c, fsdf::launch_pass(c->precision, c->cull != 0, c->lm, *P, d_pts, n, nblocks, out, c->stream,
+    HIPCHECK(c, fsdf::launch_pass(c->precision, c->cull != 0, c->lm, c->pm, d_pts, n, nblocks, out, c->stream,
                                   pe ? (hipEvent_t)pe[0] : nullptr, pe ? (hipEvent_t)pe[1] : nullptr));
     c->pass_kernel = fsdf::last_pass_kernel();
     if (prior) c->prior_ok = true;
     if (resident) c->last_pass_shape = fsdf::hpart_pass(c->lm, n) ? 2 : 1;
-    rc = release_posed(c, pbuf);
-    if (rc) return rc;
     if (prof) c->prof_used += 3;
     // the order is rebuilt on the first scheduled pass of a grid and then every
     // kOrderEvery passes (the heavy blocks of a cloud stay heavy from pass to
@@ -252,8 +224,6 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
       c->order_age[ol] = 0;
     }
   } else {
-    rc = release_posed(c, pbuf);
-    if (rc) return rc;
     HIPCHECK(c, hipMemsetAsync(d_accum, 0, (size_t)accum_len(c) * sizeof(double), c->stream));
   }
   return FSDF_OK;

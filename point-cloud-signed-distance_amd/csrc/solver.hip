@@ -46,10 +46,6 @@
 #include "pose_impl.h"
 #include "rbf_impl.h"
 
-#ifndef FSDF_SOLVER_TIMES
-#define FSDF_SOLVER_TIMES 0  // diagnostic builds: per-phase clocks of the step (iterate.hip prints them)
-#endif
-
 namespace fsdf {
 
 namespace {

@@ -10,7 +10,7 @@
 // still land in the caller's order. Hilbert rather than Morton order: a Morton
 // curve jumps at every octree boundary, so some 64-point chunks straddle two
 // distant regions and need the hulls of both; on the bench cloud the pass is
-// 8.5 % faster (0.144 -> 0.132 ms; -DFSDF_HILBERT=0 restores Morton keys).
+// 8.5 % faster (0.144 -> 0.132 ms).
 //
 // Per frame: bbox partials (<= 256 blocks) -> one-block finalize -> keys ->
 // radix sort -> gather. All scratch lives in the context (SortScratch, grown
@@ -88,9 +88,6 @@ __device__ __forceinline__ uint32_t spread10(uint32_t v) {
   return v;
 }
 
-#ifndef FSDF_HILBERT
-#define FSDF_HILBERT 1
-#endif
 // 3-D Hilbert index of 10-bit cell coordinates (Skilling's transpose form:
 // undo the excess work, Gray-encode, interleave with x most significant).
 // Unlike Morton order the curve never jumps: consecutive cells are adjacent.
@@ -132,11 +129,7 @@ __global__ __launch_bounds__(kBlock) void curve_key_kernel(const double* __restr
     int c = (int)(u * 1024.0);
     q[j] = (uint32_t)(c < 0 ? 0 : (c > 1023 ? 1023 : c));
   }
-#if FSDF_HILBERT
   keys[i] = hilbert10(q);
-#else
-  keys[i] = spread10(q[0]) | (spread10(q[1]) << 1) | (spread10(q[2]) << 2);
-#endif
   if (idx) idx[i] = (int32_t)i;
 }
 

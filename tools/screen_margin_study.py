@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""How often would the fp32 screen's batch certificate (sdf_kernels.hip
+"""How often would the fp32 screen's batch certificate (hull_sdf.h
 screen_plane_max: b2 < b1 - 2E) fail at a wider margin? (CPU study)
 
 For 800 random 64-point chunks of the bench cloud (M64, Hilbert-like Morton

@@ -4,7 +4,7 @@ item 5: the planned pass's x5/2 and x8/5 rescale of split chunks' durations).
 
 The planned pass records each chunk's wall time from its first wave's start to
 its emit; a chunk split over P waves stores that time x5/2 (P = 4) or x8/5
-(P = 2) as its serial-equivalent duration (sdf_kernels.hip planned_pass_kernel).
+(P = 2) as its serial-equivalent duration (pass_kernels.h planned_pass_kernel).
 Here the same resident cloud runs (a) every chunk on one wave (plan shares 0, 0)
 and (b) the default plan, R passes each, alternating; per chunk the median
 one-wave time and the median split wall time (the stored duration divided by
