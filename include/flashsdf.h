@@ -251,9 +251,9 @@ int fsdf_set_solver(fsdf_ctx* ctx, int32_t device_loop);
  *     moments[k][21] = Σ_{p: k*(p)=k} w_p w_pᵀ     (upper triangle, row-major:
  *                                                    00 01 .. 05 11 .. 55)
  * The two functions below are the host half of that solver: the matrix JᵀJ
- * from the moments, and one damped step. The library does not reduce the
- * moments on the device yet (today they come from the per-point outputs of
- * fsdf_eval, formed by the caller), so no solver loop of the library uses them.
+ * from the moments, and one damped step. The moments are reduced on the device
+ * (fsdf_eval_moments, fsdf_value_gradient_hessian below), and fsdf_descend_lm is
+ * the solver loop over them.
  *
  * fsdf_gauss_newton_matrix, the sibling of fsdf_config_gradient: the
  * Gauss-Newton matrix A [nq][nq] = Σ_k S_b(k) M_k S_b(k)ᵀ of the mechanism from
@@ -281,6 +281,62 @@ int fsdf_gauss_newton_matrix(int32_t nb, const int32_t* parent, const int32_t* k
  * tenfold. */
 int fsdf_lm_step(int32_t n, const double* H, const double* g, double lambda, double max_step, double* work,
                  double* dx_out);
+/* The Levenberg-Marquardt loop (host only, no device): replaces
+ * flash.tracking.LevenbergMarquardt.optimize, operation for operation — x, f,
+ * the evaluation count and the final damping are bit-identical to it. fn
+ * evaluates the objective at x: *f, g [n], H [n][n] (the Gauss-Newton Hessian);
+ * a nonzero return ends the loop with that status (x the last accepted point).
+ * One evaluation at the start x; then until iteration_limit evaluations: stop
+ * when |g|_2 (summed in index order) < tolerance; a step by fsdf_lm_step at
+ * the current damping — a degenerate one raises the damping tenfold without an
+ * evaluation; the trial x + step is accepted only when its f is lower (a NaN is
+ * not), the damping then divided by 10 (down to 1e-12), else multiplied by 10;
+ * a damping beyond 1e12 ends the loop. x [n] is updated in place; work =
+ * 3 n^2 + 5 n doubles; value_out = f at x (NaN when iteration_limit is 0),
+ * iterations_out = evaluations made, damping_out = the final damping (outputs
+ * may be NULL). */
+typedef int (*fsdf_vgh_fn)(void* user, const double* x, double* f, double* g, double* H);
+int fsdf_lm_minimize(fsdf_vgh_fn fn, void* user, int32_t n, double* x, int32_t iteration_limit, double damping,
+                     double max_step, double tolerance, double* work, double* value_out, int32_t* iterations_out,
+                     double* damping_out);
+
+/* ---- second-order solver: device side ------------------------------------------
+ * The moments above, reduced on the device (csrc/moments.hip): a launch of its
+ * own after the pass — the pass kernels are the headline path's, unchanged —
+ * over the pass's per-point k* and ∇d* in resident order, one wave per 64-point
+ * chunk, per distinct k* of the wave a masked wave sum of the 21 products into
+ * the wave's [S][21] table in LDS; every workgroup a fixed run of chunks, its
+ * waves' tables summed in wave order, the workgroups' partials in workgroup
+ * order. No floating-point atomics: for a given cloud layout the moments are
+ * bit-identical from run to run, with the planned pass on or off. All
+ * arithmetic is fp64 (fp32 contexts: their fp32 points, widened). Rigid scenes
+ * only: a scene with RBF skins or deformations is refused with FSDF_ERR_STATE,
+ * as is one whose table does not fit 64 KB of LDS (more than 390 surfaces).
+ *
+ * fsdf_eval_moments: fsdf_eval's pass over the resident cloud plus the moments,
+ * moments_out [S][21] host (required; cost_out, accum_out may be NULL).
+ * Synchronous. Replaces forming the moments on the host from fsdf_eval's
+ * per-point outputs. A cloud of no points gives zero moments.
+ *
+ * fsdf_value_gradient_hessian: fsdf_value_and_gradient plus hess_out [nq][nq] =
+ * 2 JᵀJ, the Gauss-Newton Hessian of the cost, by fsdf_gauss_newton_matrix on
+ * that pass's FK and moments. cost_out and grad_out are bit-identical to
+ * fsdf_value_and_gradient's at the same x and cloud layout. The auto regroup of
+ * the iteration entry points applies (fsdf_set_regroup), queued after the
+ * moments launch. Replaces the (c, g, H) objective a caller of
+ * LevenbergMarquardt.optimize assembled from per-point outputs.
+ *
+ * fsdf_descend_lm: fsdf_lm_minimize over fsdf_value_gradient_hessian with
+ * estimate_state's wrapped cost (src/tracking.jl:16-21): f = cost / n_points,
+ * g = grad / n_points, H / n_points — fsdf_descend's sibling for the
+ * second-order solver. A host loop: one synchronization per evaluation. x [nq]
+ * is updated in place; outputs as fsdf_lm_minimize's. */
+int fsdf_eval_moments(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out, double* moments_out);
+int fsdf_value_gradient_hessian(fsdf_ctx* ctx, const double* x, double* cost_out, double* grad_out,
+                                double* hess_out);
+int fsdf_descend_lm(fsdf_ctx* ctx, double* x, int32_t iteration_limit, double damping, double max_step,
+                    double tolerance, double n_points, double* value_out, int32_t* iterations_out,
+                    double* damping_out);
 
 /* ---- context ---------------------------------------------------------------- */
 int fsdf_create(fsdf_ctx** out, const fsdf_opts* opts);

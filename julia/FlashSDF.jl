@@ -288,6 +288,23 @@ function residual_pass!(f::GPUCost, geo::SceneGeometry, xv::Vector{Float64})
     f.memo_accum
 end
 
+"""
+One residual pass over the resident cloud of a rigid scene (poses as `device_inputs`
+returns them) with the per-surface second moments of its residual, reduced on the device
+(fsdf_eval_moments): returns (cost, accumulator, moments 21 x S — per surface the upper
+triangle, row-major, of Σ w wᵀ with w = (∇d*, p × ∇d*)), the input of a Gauss-Newton
+Hessian (fsdf_gauss_newton_matrix).
+"""
+function eval_moments(ctx::Context, poses::Vector{Float64})
+    accum = zeros(ctx.accum_len)
+    moments = zeros(21, div(length(poses), 12))
+    c = Ref{Float64}(0)
+    check(ctx.ptr, ccall((:fsdf_eval_moments, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.ptr, poses, c, accum, moments), "eval_moments")
+    c[], accum, moments
+end
+
 # Σ_p d*(p)² as a number of the state's type: the value from the pass; for a
 # Dual chunk, the first-order change of the cost through every surface pose
 # (δc = −(ω·(M − t×F) + δt·F) with ω = vee(δR Rᵀ)) and every RBF skin's

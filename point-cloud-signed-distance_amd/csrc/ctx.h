@@ -152,6 +152,10 @@ struct fsdf_ctx {
   int64_t plan_max_points = -1;      // planned pass up to this cloud size (per device; -1: the model's default)
   fsdf::DevBuf<int32_t> kstar;       // per-point outputs (fsdf_eval, fsdf_skin, fsdf_raycast)
   fsdf::DevBuf<double> d, grad;
+  // second moments of the residual (fsdf_eval_moments, fsdf_value_gradient_hessian;
+  // moments.hip): the workgroups' partials, the [S][21] sums, their pinned read-back
+  fsdf::DevBuf<double> moments_partials, moments;
+  fsdf::PinnedBuf<double> h_moments;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;
@@ -165,6 +169,7 @@ struct fsdf_ctx {
     std::vector<int32_t> parent, kind, qoff, surface_body;
     std::vector<double> axis, AR, At, BR, Bt, frame_R, frame_t;
     std::vector<double> R, t, Rb, tb, poses, work;  // scratch
+    std::vector<double> gn_work;                    // fsdf_gauss_newton_matrix's (fsdf_value_gradient_hessian)
     // RBF surfaces (fsdf_set_rbf_centres), in surface order; n == 0: undeclared
     struct Rbf {
       int n_sp = 0, n = 0;
@@ -227,6 +232,8 @@ int run_pass(fsdf_ctx* c, const double* poses, const void* d_pts, int64_t n, dou
              const int* skip = nullptr);
 int ensure_outputs(fsdf_ctx* c, int64_t n);
 int ensure_host_acc(fsdf_ctx* c, int len);
+// (the pass with k*, ∇d* in resident order, then the moments: h_acc and h_moments in flight)
+int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who);
 int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
           double* grad_out, bool want_pp);
 #pragma GCC visibility pop

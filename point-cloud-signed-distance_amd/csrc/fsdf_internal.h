@@ -232,6 +232,35 @@ hipError_t launch_reduce(const double* partials, int nblocks, int len, double* d
                          hipStream_t s, const uint32_t* cost = nullptr, int32_t* order = nullptr,
                          hipEvent_t ev_stop = nullptr, const int* skip = nullptr);
 
+// ---- second moments of the residual (moments.hip) -----------------------------
+// Per surface k the 21 upper-triangle entries (row-major) of Σ w wᵀ over the
+// resident points with k* = k, w = (∇d*, p × ∇d*), from the per-point k* and
+// ∇d* a pass wrote in RESIDENT order. Workgroup g sums the chunks
+// [g · run, (g + 1) · run), every wave a contiguous share of them into an
+// [S][21] table of its own in LDS, and writes the waves' tables, summed in
+// wave order, as one partial (line tiles, as the pass's); launch_reduce sums
+// the partials in workgroup order. run = moments_run(n): at least
+// kMomentsMinChunks, and as many as keep the grid at kMomentsMaxGroups
+// workgroups (two per CU: 5.5 MB of partials for 64 surfaces) — a function of
+// n alone; moments_waves(S) waves per workgroup, as many of 4, 2, 1 as have
+// room for their tables in kMomentsMaxLds (4 up to 97 surfaces, 2 up to 195, 1
+// up to 390).
+constexpr int kMomentsLen = 21;          // entries per surface
+constexpr int kMomentsBlock = 256;       // 4 waves at most
+constexpr int kMomentsMinChunks = 8;     // a workgroup's run of 64-point chunks, at least (a multiple of 4)
+constexpr int kMomentsMaxGroups = 512;   // workgroups, at most
+constexpr int kMomentsMaxLds = 65536;    // the workgroup's tables
+int moments_waves(int S);  // 0: not even one table fits
+int64_t moments_run(int64_t n);
+int moments_groups(int64_t n);
+bool moments_fit(int S);  // the scene's table fits kMomentsMaxLds
+// doubles of d_partials for a cloud of n points (>= one workgroup's)
+size_t moments_partials_len(int64_t n, int S);
+// n > 0, moments_fit(S). d_pts: the resident cloud (precision 64 / 32; all
+// arithmetic fp64); d_moments [S][21]. A k* outside [0, S) contributes nothing.
+hipError_t launch_moments(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_grad, int64_t n,
+                          int S, double* d_partials, double* d_moments, hipStream_t s);
+
 hipError_t launch_to_f32(const double* src, float* dst, int64_t count, hipStream_t s);
 
 // per-chunk (64 points) bounding spheres of a resident cloud of the context

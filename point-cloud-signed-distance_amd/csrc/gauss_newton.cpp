@@ -1,6 +1,7 @@
 // gauss_newton.cpp — host side of the second-order tracking solver (no device):
 // the Gauss-Newton matrix of the mechanism from the per-surface second moments
-// of the residual, and one damped (Levenberg-Marquardt) step.
+// of the residual, one damped (Levenberg-Marquardt) step, and the loop over it
+// (fsdf_lm_minimize).
 //
 // For a point p on a surface of body b, ∂d*(p)/∂x_i = s_i · w_p, with w_p =
 // (∇d*, p × ∇d*) and s_i the motion row of joint coordinate i — the row the
@@ -177,5 +178,72 @@ extern "C" int fsdf_lm_step(int32_t n, const double* H, const double* g, double 
     const double lo = s < -max_step ? -max_step : s;
     dx_out[i] = max_step < lo ? max_step : lo;
   }
+  return FSDF_OK;
+}
+
+// flash.tracking.LevenbergMarquardt.optimize, operation for operation (the
+// same bits): |g| summed in index order; a degenerate step raises lambda
+// without an evaluation; a trial is accepted only when ft < f (a NaN ft is
+// rejected); lambda / 10 down to 1e-12 on acceptance, x 10 up to 1e12 on
+// rejection, the loop ending once it passes 1e12.
+// work: g | H | xt | gt | Ht | step | fsdf_lm_step's n^2 + n
+extern "C" int fsdf_lm_minimize(fsdf_vgh_fn fn, void* user, int32_t n, double* x, int32_t iteration_limit,
+                                double damping, double max_step, double tolerance, double* work, double* value_out,
+                                int32_t* iterations_out, double* damping_out) {
+  if (iterations_out) *iterations_out = 0;
+  if (damping_out) *damping_out = damping;
+  if (!fn || n < 0 || iteration_limit < 0 || (n > 0 && !x) || !work) return FSDF_ERR_ARG;
+  const size_t nn = (size_t)n * n;
+  double* g = work;
+  double* H = g + n;
+  double* xt = H + nn;
+  double* gt = xt + n;
+  double* Ht = gt + n;
+  double* step = Ht + nn;
+  double* step_work = step + n;
+  double lam = damping, f = NAN;
+  int it = 0;
+  if (iteration_limit > 0) {
+    const int rc = fn(user, x, &f, g, H);
+    if (rc) return rc;
+    it = 1;
+    if (iterations_out) *iterations_out = it;
+  }
+  while (it < iteration_limit) {
+    double nrm2 = 0.0;
+    for (int i = 0; i < n; ++i) nrm2 += g[i] * g[i];
+    if (sqrt(nrm2) < tolerance) break;
+    const int st = fsdf_lm_step(n, H, g, lam, max_step, step_work, step);
+    if (st == FSDF_ERR_DEGENERATE) {  // more damping, no evaluation
+      lam *= 10.0;
+      if (lam > 1e12) break;
+      continue;
+    }
+    if (st) return st;
+    for (int i = 0; i < n; ++i) xt[i] = x[i] + step[i];
+    double ft = NAN;
+    const int rc = fn(user, xt, &ft, gt, Ht);
+    if (rc) {
+      if (damping_out) *damping_out = lam;
+      if (value_out) *value_out = f;
+      return rc;
+    }
+    ++it;
+    if (iterations_out) *iterations_out = it;
+    if (ft < f) {
+      f = ft;
+      for (int i = 0; i < n; ++i) {
+        x[i] = xt[i];
+        g[i] = gt[i];
+      }
+      for (size_t i = 0; i < nn; ++i) H[i] = Ht[i];
+      lam = 1e-12 > lam / 10.0 ? 1e-12 : lam / 10.0;
+    } else {
+      lam *= 10.0;
+      if (lam > 1e12) break;
+    }
+  }
+  if (damping_out) *damping_out = lam;
+  if (value_out) *value_out = f;
   return FSDF_OK;
 }

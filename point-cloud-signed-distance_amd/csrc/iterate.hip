@@ -1,7 +1,9 @@
 // iterate.hip — iterations of a registered mechanism: fsdf_set_mechanism, RBF
 // centres and deformations, the host halves of one CostFunctor iteration
-// (FK, weight solve, chain rule) around a pass, and the solver loops of
-// fsdf_descend on the host and on the device (solver.hip).
+// (FK, weight solve, chain rule) around a pass, the same with the Gauss-Newton
+// Hessian (fsdf_value_gradient_hessian) and its Levenberg-Marquardt loop
+// (fsdf_descend_lm), and the solver loops of fsdf_descend on the host and on
+// the device (solver.hip).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -294,6 +296,79 @@ extern "C" int fsdf_value_and_gradient(fsdf_ctx* c, const double* x, double* cos
   ++g_host_n;
 #endif
   return rc;
+}
+
+// fsdf_value_and_gradient with the Gauss-Newton Hessian 2 JᵀJ of the same pass
+// (rigid scenes): the pass also writes k* and ∇d* in resident order, the
+// moments launch (moments.hip) reduces them per surface, and
+// fsdf_gauss_newton_matrix contracts them with that pass's FK. The auto
+// regroup is queued after the moments launch: they read the layout the pass
+// ran on.
+extern "C" int fsdf_value_gradient_hessian(fsdf_ctx* c, const double* x, double* cost_out, double* grad_out,
+                                           double* hess_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (!x || !cost_out || !grad_out || !hess_out)
+    return fail(c, FSDF_ERR_ARG, "value_gradient_hessian: null argument");
+  if (c->lm.R > 0 || c->mech.n_deform > 0)
+    return fail(c, FSDF_ERR_STATE,
+                "value_gradient_hessian: the Gauss-Newton matrix is defined for rigid scenes (no RBF skin, no "
+                "deformation)");
+  int rc = iteration_prepare(c, x, "value_gradient_hessian");
+  if (rc) return rc;
+  auto& M = c->mech;
+  rc = run_pass_moments(c, M.poses.data(), "value_gradient_hessian");
+  if (rc) return rc;
+  rc = iteration_regroup(c);  // (stream-ordered after the pass and the moments: the sync below covers it)
+  if (rc) return rc;
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  rc = iteration_finish(c, x, c->h_acc.get(), cost_out, grad_out, "value_gradient_hessian");
+  if (rc) return rc;
+  const int nq = M.nq;
+  M.gn_work.resize((size_t)36 * M.nb + (size_t)6 * nq);
+  rc = fsdf_gauss_newton_matrix(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.Rb.data(),
+                                M.tb.data(), x, c->lm.S, M.surface_body.data(), c->h_moments.get(), nq,
+                                M.gn_work.data(), hess_out);
+  if (rc) return fail(c, rc, "value_gradient_hessian: Gauss-Newton matrix");
+  for (size_t i = 0; i < (size_t)nq * nq; ++i) hess_out[i] = 2.0 * hess_out[i];
+  return FSDF_OK;
+}
+
+// fsdf_lm_minimize (gauss_newton.cpp) over fsdf_value_gradient_hessian with
+// estimate_state's wrapped cost (c / n, ∂c/∂x / n, H / n): the host loop, one
+// synchronization per evaluation.
+namespace {
+struct LmObjective {
+  fsdf_ctx* c;
+  int nq;
+  double n_points;
+};
+int lm_objective(void* user, const double* x, double* f, double* g, double* H) {
+  const LmObjective& o = *(const LmObjective*)user;
+  double cost = 0.0;
+  const int rc = fsdf_value_gradient_hessian(o.c, x, &cost, g, H);
+  if (rc) return rc;
+  *f = cost / o.n_points;
+  for (int i = 0; i < o.nq; ++i) g[i] = g[i] / o.n_points;
+  for (size_t i = 0; i < (size_t)o.nq * o.nq; ++i) H[i] = H[i] / o.n_points;
+  return FSDF_OK;
+}
+}  // namespace
+
+extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, double damping, double max_step,
+                               double tolerance, double n_points, double* value_out, int32_t* iterations_out,
+                               double* damping_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (iterations_out) *iterations_out = 0;
+  if (!x || iteration_limit < 0 || !(n_points > 0.0) || !std::isfinite(damping) || !(max_step >= 0.0))
+    return fail(c, FSDF_ERR_ARG, "descend_lm: bad arguments");
+  if (c->mech.nb == 0) return fail(c, FSDF_ERR_STATE, "descend_lm: no mechanism (call fsdf_set_mechanism)");
+  if (c->lm.R > 0 || c->mech.n_deform > 0)
+    return fail(c, FSDF_ERR_STATE, "descend_lm: rigid scenes only (no RBF skin, no deformation)");
+  const int nq = c->mech.nq;
+  LmObjective o{c, nq, n_points};
+  std::vector<double> work((size_t)3 * nq * nq + (size_t)5 * nq + 1);
+  return fsdf_lm_minimize(lm_objective, &o, nq, x, iteration_limit, damping, max_step, tolerance, work.data(),
+                          value_out, iterations_out, damping_out);
 }
 
 // The solver loop of estimate_state (src/tracking.jl:16-26 with the

@@ -1,7 +1,8 @@
 // pass.hip — one residual pass of a context (pose -> pass -> reduce): the
 // partial sums, the pose ring, the planned pass and its plan, the per-point
-// outputs and their read-back, fsdf_eval / fsdf_eval_device and the
-// permutation getters.
+// outputs and their read-back, fsdf_eval / fsdf_eval_device, the permutation
+// getters, and the pass followed by the second-moments reduction
+// (run_pass_moments, fsdf_eval_moments).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -333,4 +334,71 @@ extern "C" int fsdf_eval(fsdf_ctx* c, const double* poses, double* cost_out, dou
                     want_pp ? c->d.get() : nullptr, want_pp ? c->grad.get() : nullptr, out_perm(c), true);
   if (rc) return rc;
   return fetch(c, c->n, cost_out, accum_out, kstar_out, d_out, grad_out, want_pp);
+}
+
+// One pass over the resident cloud and the per-surface second moments of its
+// residual (moments.hip), for fsdf_eval_moments and
+// fsdf_value_gradient_hessian: the accumulator goes to c->h_acc (stored by the
+// reduction itself, as fsdf_value_and_gradient's), the moments [S][21] to
+// c->h_moments, both in flight on the context stream when this returns — the
+// caller synchronises, and regroups (if it does) after this, so the moments
+// read the layout the pass ran on.
+// The order here is the rule of device_buffers.h made structural: (1) every
+// buffer the pass's per-point outputs and the moments touch is reserved; (2)
+// only then are their pointers read with get(), into locals; (3) the launches
+// take those locals. No context buffer is named as an argument of a call that
+// may reserve. A cloud of no points launches no moments kernel: zero moments.
+int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who) {
+  const int S = c->lm.S;
+  if (c->lm.R > 0 || c->mech.n_deform > 0)
+    return fail(c, FSDF_ERR_STATE, "%s: the second moments are defined for rigid scenes (no RBF skin, no deformation)",
+                who);
+  if (!fsdf::moments_fit(S))
+    return fail(c, FSDF_ERR_STATE, "%s: the moments table of %d surfaces (%zu bytes) does not fit %d bytes of LDS", who,
+                S, (size_t)S * fsdf::kMomentsLen * sizeof(double), fsdf::kMomentsMaxLds);
+  const int64_t n = c->n;
+  const size_t mlen = (size_t)S * fsdf::kMomentsLen;
+  // (1) reserve
+  int rc = ensure_outputs(c, n);
+  if (rc) return rc;
+  rc = ensure_host_acc(c, accum_len(c));
+  if (rc) return rc;
+  HIPCHECK(c, c->moments_partials.reserve(fsdf::moments_partials_len(n, S)));
+  HIPCHECK(c, c->moments.reserve(mlen));
+  HIPCHECK(c, c->h_moments.reserve(mlen));
+  // (2) read the pointers
+  const void* d_pts = c->cur.pts.get();
+  int32_t* d_kstar = c->kstar.get();
+  double* d_grad = c->grad.get();
+  double* d_partials = c->moments_partials.get();
+  double* d_moments = c->moments.get();
+  double* h_moments = c->h_moments.get();
+  double* d_acc_host = nullptr;
+  HIPCHECK(c, hipHostGetDevicePointer((void**)&d_acc_host, c->h_acc.get(), 0));
+  // (3) launch: the pass with k* and ∇d* in resident order (no permutation), the moments, their read-back
+  rc = run_pass(c, poses, d_pts, n, d_acc_host, d_kstar, nullptr, d_grad, nullptr, true);
+  if (rc) return rc;
+  if (n == 0) {
+    memset(h_moments, 0, mlen * sizeof(double));
+    return FSDF_OK;
+  }
+  HIPCHECK(c, fsdf::launch_moments(c->precision, d_pts, d_kstar, d_grad, n, S, d_partials, d_moments, c->stream));
+  HIPCHECK(c, hipMemcpyAsync(h_moments, d_moments, mlen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_eval_moments(fsdf_ctx* c, const double* poses, double* cost_out, double* accum_out,
+                                 double* moments_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval_moments: no model (call fsdf_set_model first)");
+  if (!poses || !moments_out) return fail(c, FSDF_ERR_ARG, "eval_moments: poses and moments_out are required");
+  HIPCHECK(c, hipSetDevice(c->device));
+  const int rc = run_pass_moments(c, poses, "eval_moments");
+  if (rc) return rc;
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  const double* acc = c->h_acc.get();
+  if (cost_out) *cost_out = acc[0];
+  if (accum_out) memcpy(accum_out, acc, (size_t)accum_len(c) * sizeof(double));
+  memcpy(moments_out, c->h_moments.get(), (size_t)c->lm.S * fsdf::kMomentsLen * sizeof(double));
+  return FSDF_OK;
 }

@@ -107,7 +107,16 @@ _PROTOS = {
     "fsdf_gauss_newton_matrix": (c_int32, [c_int32] + [c_void_p] * 7 + [c_int32] + [c_void_p] * 2 + [c_int32] +
                                  [c_void_p] * 2),
     "fsdf_lm_step": (c_int32, [c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p]),
+    "fsdf_lm_minimize": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double,
+                                   c_void_p, POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
+    "fsdf_eval_moments": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
+    "fsdf_value_gradient_hessian": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
+    "fsdf_descend_lm": (c_int32, [c_void_p, c_void_p, c_int32, c_double, c_double, c_double, c_double,
+                                  POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
 }
+# fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
+VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
+                          POINTER(c_double))
 SYMBOLS = tuple(_PROTOS)
 
 _lib = None
@@ -188,6 +197,45 @@ def lm_step(H, g, damping: float, max_step: float):
     if st != FSDF_OK:
         raise FlashNativeError(st, "fsdf_lm_step: bad arguments")
     return st, dx
+
+
+def lm_minimize(value_gradient_hessian, x0, iteration_limit: int, damping: float, max_step: float,
+                tolerance: float):
+    """fsdf_lm_minimize: the Levenberg-Marquardt loop of
+    flash.tracking.LevenbergMarquardt.optimize natively (host only), over a
+    Python objective x -> (f, g, H). The objective may instead return a nonzero
+    int: the loop ends and FlashNativeError carries that status; an exception
+    it raises ends the loop too and is raised again here. Returns (x, f,
+    evaluations, final damping); f is None when iteration_limit is 0."""
+    x = np.array(x0, np.float64, copy=True).reshape(-1)
+    n = x.size
+    raised = []
+
+    def fn(_user, px, pf, pg, pH):
+        try:
+            out = value_gradient_hessian(np.ctypeslib.as_array(px, (n,)).copy())
+            if isinstance(out, (int, np.integer)):
+                return int(out)
+            f, g, H = out
+            pf[0] = float(f)
+            np.ctypeslib.as_array(pg, (n,))[:] = np.asarray(g, np.float64).reshape(n)
+            np.ctypeslib.as_array(pH, (n, n))[:] = np.asarray(H, np.float64).reshape(n, n)
+            return 0
+        except BaseException as e:  # (an exception cannot cross the C frames)
+            raised.append(e)
+            return 1
+
+    work = np.empty(3 * n * n + 5 * n + 1)
+    f, its, lam = c_double(0.0), c_int32(0), c_double(0.0)
+    cb = VGH_FN(fn)
+    st = load().fsdf_lm_minimize(ctypes.cast(cb, c_void_p), None, n, ptr(x), int(iteration_limit), float(damping),
+                                 float(max_step), float(tolerance), ptr(work), ctypes.byref(f), ctypes.byref(its),
+                                 ctypes.byref(lam))
+    if raised:
+        raise raised[0]
+    if st != FSDF_OK:
+        raise FlashNativeError(st, "fsdf_lm_minimize: the objective's status, or bad arguments")
+    return x, (f.value if iteration_limit > 0 else None), its.value, lam.value
 
 
 class Context:
@@ -377,6 +425,18 @@ class Context:
               self._ctx, "eval")
         return cost.value, accum, (kstar, d, grad)
 
+    def eval_moments(self, poses):
+        """fsdf_eval_moments: one pass over the resident cloud and the
+        per-surface second moments of its residual, reduced on the device ->
+        (cost, accum, moments [K, 21]). Rigid scenes."""
+        p = self._poses(poses)
+        accum = np.empty(self.accum_len, np.float64)
+        mom = np.empty((self.K, 21), np.float64)
+        cost = c_double(0.0)
+        check(self._lib.fsdf_eval_moments(self._ctx, ptr(p), ctypes.byref(cost), ptr(accum), ptr(mom)), self._ctx,
+              "eval_moments")
+        return cost.value, accum, mom
+
     def eval_device(self, poses, d_accum: int, d_kstar: int = 0, d_d: int = 0, d_grad: int = 0):
         """Asynchronous pass writing into device buffers (raw device pointers)."""
         p = self._poses(poses)
@@ -523,6 +583,28 @@ class Context:
         check(self._lib.fsdf_value_and_gradient(self._ctx, ptr(x), ctypes.byref(c), ptr(g)), self._ctx,
               "value_and_gradient")
         return c.value, g
+
+    def value_gradient_hessian(self, x):
+        """(cost, ∂cost/∂x, the Gauss-Newton Hessian 2 JᵀJ) in one native call
+        (fsdf_value_gradient_hessian; rigid scenes)."""
+        x = self._state_vector(x, "value_gradient_hessian")
+        g = np.empty(x.size)  # (nq: a scene with deformations is refused)
+        H = np.empty((x.size, x.size))
+        c = c_double(0.0)
+        check(self._lib.fsdf_value_gradient_hessian(self._ctx, ptr(x), ctypes.byref(c), ptr(g), ptr(H)), self._ctx,
+              "value_gradient_hessian")
+        return c.value, g, H
+
+    def descend_lm(self, x, iteration_limit, damping, max_step, tolerance=0.0, n_points=1.0):
+        """fsdf_descend_lm: the Levenberg-Marquardt loop over
+        value_gradient_hessian natively. Returns (x, f at x, evaluations made,
+        final damping)."""
+        x = np.array(self._state_vector(x, "descend_lm"), copy=True)
+        f, it, lam = c_double(0.0), c_int32(0), c_double(0.0)
+        check(self._lib.fsdf_descend_lm(self._ctx, ptr(x), int(iteration_limit), float(damping), float(max_step),
+                                        float(tolerance), float(n_points), ctypes.byref(f), ctypes.byref(it),
+                                        ctypes.byref(lam)), self._ctx, "descend_lm")
+        return x, f.value, it.value, lam.value
 
     def descend(self, x, iteration_limit, rate, max_step, tolerance=0.0, divisors=None, n_points=1.0):
         """fsdf_descend: the NaiveSolver loop over value_and_gradient natively.

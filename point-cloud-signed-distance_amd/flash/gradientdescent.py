@@ -126,6 +126,10 @@ class CostFunctor:
         # the whole iteration (FK, RBF weight solve, pass, chain rule,
         # regularizer) in one native call (fsdf_value_and_gradient)
         self._native = native_capable(manipulator)
+        # rigid: hulls only, nothing deformable — the scenes with a Gauss-Newton
+        # Hessian (value_gradient_hessian, descend_lm)
+        self.rigid = all(isinstance(s, ConvexGeometry) for s in manipulator.surfaces) and \
+            manipulator.num_deformations() == 0
         if self._native and getattr(self.ctx, "_mechanism_of", None) != (manipulator, self.weight):
             self._register_native()
 
@@ -199,6 +203,27 @@ class CostFunctor:
         if getattr(self.ctx, "_mechanism_of", None) != (self.manipulator, self.weight):
             self._register_native()
         return self.ctx.descend(x, iteration_limit, rate, max_step, tolerance, divisors, n_points)
+
+    def _native_rigid(self, who):
+        if not (self._native and self.rigid):
+            raise NotImplementedError(f"{who}: rigid native scenes only (no RBF skin, no deformation)")
+        self._ensure_resident()
+        if getattr(self.ctx, "_mechanism_of", None) != (self.manipulator, self.weight):
+            self._register_native()
+
+    def value_gradient_hessian(self, x):
+        """(c(x), ∂c/∂x, the Gauss-Newton Hessian 2 JᵀJ) from one residual pass
+        and the device reduction of its second moments
+        (fsdf_value_gradient_hessian); rigid scenes."""
+        self._native_rigid("value_gradient_hessian")
+        return self.ctx.value_gradient_hessian(np.asarray(x, np.float64))
+
+    def descend_lm(self, x, iteration_limit, damping, max_step, tolerance=0.0, n_points=1.0):
+        """The LevenbergMarquardt loop over value_gradient_hessian in one native
+        call (fsdf_descend_lm); rigid scenes. Returns (x, f, evaluations, final
+        damping)."""
+        self._native_rigid("descend_lm")
+        return self.ctx.descend_lm(x, iteration_limit, damping, max_step, tolerance, n_points)
 
     def per_point(self, x):
         """(d*, k*, ∇d*) for every sensed point at configuration x."""

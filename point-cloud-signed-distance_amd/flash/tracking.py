@@ -87,8 +87,11 @@ class LevenbergMarquardt:
     surface points, start off by σ = 0.2 rad) it is at the cloud's floor
     f(q_true) = 2.83e-4 after 4 evaluations, where NaiveSolver(rate 0.1,
     max_step 0.5) is at 6.12e-4 after 30 (tests/test_gauss_newton.py).
-    estimate_state does not take it yet: CostFunctor has no Hessian, because
-    the second moments are not reduced on the device."""
+    estimate_state, Tracker and track take it for native rigid scenes: the
+    second moments are reduced on the device (fsdf_value_gradient_hessian), and
+    without a callback the whole loop runs natively (fsdf_descend_lm, the same
+    bits). Scenes with RBF skins or deformations have no Gauss-Newton matrix
+    here: NotImplementedError."""
     num_vars: int
     damping: float = 1e-3
     max_step: float = 0.5
@@ -141,7 +144,8 @@ def _default_solver(manipulator):
 def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
     """wrapped_cost (src/tracking.jl:16-21) over a CostFunctor, then optimize!.
     Without a callback, a NaiveSolver runs natively (fsdf_descend: the same
-    arithmetic, no Python round trip per iteration)."""
+    arithmetic, no Python round trip per iteration), and so does a
+    LevenbergMarquardt on a native rigid scene (fsdf_descend_lm)."""
     n = max(n_points, 1)
     if callback is None and type(solver) is NaiveSolver and cost._native:
         x0 = np.asarray(x_estimated, np.float64)
@@ -153,10 +157,27 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
         solver.iterations = its
         return x
     if isinstance(solver, LevenbergMarquardt):
-        # its objective returns (f, g, H); a CostFunctor has no Hessian yet (the
-        # second moments of the residual are not reduced on the device)
-        raise NotImplementedError("estimate_state: LevenbergMarquardt needs an objective with a Gauss-Newton "
-                                  "Hessian; call its optimize() with one (CostFunctor does not provide it yet)")
+        # its objective returns (f, g, H): native rigid scenes have the Hessian
+        # (the second moments of the residual, reduced on the device)
+        if not (cost._native and getattr(cost, "rigid", True) and hasattr(cost, "value_gradient_hessian")):
+            raise NotImplementedError("estimate_state: LevenbergMarquardt needs an objective with a Gauss-Newton "
+                                      "Hessian: a native rigid scene (no RBF skin, no deformation); or call its "
+                                      "optimize() with one")
+        x0 = np.asarray(x_estimated, np.float64)
+        if callback is None and type(solver) is LevenbergMarquardt and hasattr(cost, "descend_lm"):
+            x, _, its, lam = cost.descend_lm(x0, solver.iteration_limit, solver.damping, solver.max_step,
+                                             solver.gradient_convergence_tolerance, n)
+            solver.iterations, solver.final_damping = its, lam
+            return x
+
+        def wrapped_h(x):
+            c, g, H = cost.value_gradient_hessian(x)
+            if callback is not None:
+                callback(x, c)
+            return c / n, g / n, H / n
+
+        x, _ = solver.optimize(wrapped_h, x0)
+        return x
 
     def wrapped(x):
         c, g = cost.value_and_gradient(x)

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""What the Gauss-Newton Hessian costs beside a gradient (GPU box): per call,
+fsdf_value_gradient_hessian (pass + per-point k*, ∇d* + the moments launch and
+its reduce + read-back + the host matrix) against fsdf_value_and_gradient on
+the same resident cloud, alternating, in its steady layout (after the cloud's
+first pass and auto regroup).
+
+    python3 tools/lm_probe.py m64:1048576 m64:131072 irb140:1048576 [--reps R] [--json OUT.jsonl]
+
+    python3 tools/lm_probe.py m64:1048576 --frames 5
+
+times whole estimate_state frames instead (set_points + the solver from the
+same perturbed start, as tools/descend_probe.py's): the default NaiveSolver
+(30 iterations, rate 0.1, max_step 0.5, tolerance 1e-3) against
+LevenbergMarquardt at several evaluation limits, with the f = c / n each ends
+at and the evaluations it made.
+
+And for the kernels' own times a kernel trace of the Hessian calls alone
+(no counters in the same run):
+
+    rocprofv3 --kernel-trace --output-format csv -d OUT -o run -- python3 tools/lm_probe.py m64:1048576 --hessian-only
+    python3 tools/lm_probe.py --trace OUT/.../run_kernel_trace.csv
+
+which prints per kernel the count, mean and median duration, and for
+moments_kernel the span to the end of the tile reduce that follows it."""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "point-cloud-signed-distance_amd"))
+
+
+def run(a):
+    import torch  # noqa: F401  (the HIP runtime torch loads, before libflashsdf)
+    from flash import Models, synthetic
+    from flash.gradientdescent import CostFunctor
+    for cfg in a.configs:
+        model, n = cfg.split(":")
+        n = int(n)
+        m = Models.arm_grid() if model == "m64" else Models.irb140()
+        q_true, q = synthetic.perturbed_configuration(m, 1234)
+        q = np.asarray(q, np.float64)
+        cf = CostFunctor(m, synthetic.depth_cloud(m, q_true, n, seed=1234 + 17))
+        for _ in range(5):  # the cloud's first pass, the regroup, the block order / plan, allocations
+            cf.value_and_gradient(q)
+            cf.value_gradient_hessian(q)
+        vg, vgh = [], []
+        for _ in range(a.reps):
+            if not a.hessian_only:
+                t0 = time.perf_counter()
+                cf.value_and_gradient(q)
+                vg.append((time.perf_counter() - t0) * 1e6)
+            t0 = time.perf_counter()
+            cf.value_gradient_hessian(q)
+            vgh.append((time.perf_counter() - t0) * 1e6)
+        out = {"model": model, "points": n, "reps": a.reps, "pass_kernel": cf.ctx.pass_kernel_name(),
+               "value_gradient_hessian_us": statistics.median(vgh),
+               "value_gradient_hessian_us_p10_p90": [float(np.percentile(vgh, 10)), float(np.percentile(vgh, 90))]}
+        if vg:
+            out["value_and_gradient_us"] = statistics.median(vg)
+            out["value_and_gradient_us_p10_p90"] = [float(np.percentile(vg, 10)), float(np.percentile(vg, 90))]
+            out["hessian_extra_us"] = out["value_gradient_hessian_us"] - out["value_and_gradient_us"]
+        print(json.dumps(out), flush=True)
+        if a.json:
+            with open(a.json, "a") as f:
+                f.write(json.dumps(out) + "\n")
+
+
+def frames(a):
+    import torch  # noqa: F401
+    from flash import Models, synthetic
+    from flash.gradientdescent import CostFunctor
+    for cfg in a.configs:
+        model, n = cfg.split(":")
+        n = int(n)
+        m = Models.arm_grid() if model == "m64" else Models.irb140()
+        q_true, q = synthetic.perturbed_configuration(m, 1234)
+        q = np.asarray(q, np.float64)
+        pts = synthetic.depth_cloud(m, q_true, n, seed=1234 + 17)
+        cf = CostFunctor(m, pts)
+        f_true = cf.value_and_gradient(np.asarray(q_true, np.float64))[0] / n
+        solvers = [("naive", None)] + [("lm", k) for k in (3, 4, 6, 10)]
+        for rep in range(2):  # (alternating: each solver's frames twice, apart)
+            for name, limit in solvers:
+                ms = []
+                for _ in range(a.frames + 1):
+                    t0 = time.perf_counter()
+                    cf.set_sensed_points(pts)
+                    if name == "naive":
+                        x, f, its = cf.descend(q, 30, 0.1, 0.5, 1e-3, None, float(n))
+                    else:
+                        x, f, its, _ = cf.descend_lm(q, limit, 1e-3, 0.5, 1e-6, float(n))
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                out = {"model": model, "points": n, "solver": name, "limit": limit or 30, "rep": rep,
+                       "frame_ms": statistics.median(ms[1:]), "evaluations": its, "f": f, "f_at_q_true": f_true,
+                       "max_abs_q_error": float(np.abs(x - q_true).max())}
+                print(json.dumps(out), flush=True)
+                if a.json:
+                    with open(a.json, "a") as fh:
+                        fh.write(json.dumps(out) + "\n")
+
+
+def trace(path):
+    rows = list(csv.DictReader(open(path)))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    by = {}
+    for r in rows:
+        name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void ", "")[:70]
+        by.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name, v in sorted(by.items(), key=lambda kv: -sum(kv[1])):
+        print(f"{name:70s} {len(v):6d} x {statistics.mean(v):8.2f} us (median {statistics.median(v):.2f})")
+    spans, red, gap = [], [], []
+    for i, r in enumerate(rows[:-1]):
+        nxt = rows[i + 1]
+        if "moments_kernel" in r["Kernel_Name"] and "reduce_tiles_kernel" in nxt["Kernel_Name"]:
+            spans.append((int(nxt["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+            red.append((int(nxt["End_Timestamp"]) - int(nxt["Start_Timestamp"])) / 1e3)
+            if i > 0:
+                gap.append((int(r["Start_Timestamp"]) - int(rows[i - 1]["End_Timestamp"])) / 1e3)
+    if spans:
+        print(f"moments + reduce: span {statistics.median(spans):.2f} us (its reduce {statistics.median(red):.2f} us; "
+              f"idle before the moments launch {statistics.median(gap):.2f} us), median over {len(spans)}")
+
+
+if __name__ == "__main__":
+    p = argparse.ArgumentParser()
+    p.add_argument("configs", nargs="*", default=["m64:1048576"])
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--hessian-only", action="store_true")
+    p.add_argument("--json", default=None)
+    p.add_argument("--trace", default=None)
+    p.add_argument("--frames", type=int, default=0)
+    a = p.parse_args()
+    if a.trace:
+        trace(a.trace)
+    elif a.frames:
+        frames(a)
+    else:
+        run(a)

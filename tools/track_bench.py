@@ -5,7 +5,11 @@ moving model, each frame = one cloud swap (upload + device sort) + I solver
 iterations (native FK + pose assembly, residual pass, accumulator read-back,
 chain rule). Prints ms per iteration, ms per frame, tracking error.
 
-    python tools/track_bench.py [--model m64|irb140|c5] [--points N] [--frames F] [--iters I]
+    python tools/track_bench.py [--model m64|irb140|c5] [--points N] [--frames F] [--iters I] [--solver naive|lm]
+
+--solver lm: the frames run LevenbergMarquardt (fsdf_descend_lm; rigid models
+only) with --iters as its evaluation limit; its default tolerance ends a frame
+early. Either way the output lists each frame's evaluations and final f = c / n.
 
 c5 = the notebook's own scene (irb_and_squishable: 7 hulls + the deformable
 squishable RBF skin + table, 63 states): the IRB's joints move between
@@ -28,11 +32,12 @@ def main():
     ap.add_argument("--points", type=int, default=1 << 20)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--solver", default="naive", choices=("naive", "lm"))
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import flash
     from flash import Models, synthetic
-    from flash.tracking import NaiveSolver, Tracker
+    from flash.tracking import LevenbergMarquardt, NaiveSolver, Tracker
     rng = np.random.Generator(np.random.PCG64(91))
     if a.model == "c5":
         from bench_configs import rbf_cloud
@@ -59,14 +64,22 @@ def main():
     # step rules: irb140.ipynb's rate 20 for the rigid arms; irb_and_squishable.ipynb
     # cell 11's rate 0.5 / max_step 0.1 for its own scene (30 iterations per frame here)
     rate = 0.5 if a.model == "c5" else 20.0
-    tr = Tracker(m, state, NaiveSolver(n, rate=rate, max_step=0.1, iteration_limit=a.iters))
+    if a.solver == "lm":
+        if a.model == "c5":
+            ap.error("--solver lm: rigid models only (m64, irb140)")
+        solver = LevenbergMarquardt(n, iteration_limit=a.iters)
+    else:
+        solver = NaiveSolver(n, rate=rate, max_step=0.1, iteration_limit=a.iters)
+    tr = Tracker(m, state, solver)
     tr.step(clouds[0])  # warm-up frame (allocations)
     tr.frame_ms.clear(); tr.set_points_ms.clear(); tr.iterations.clear()
-    errs = []
+    errs, final_f = [], []
     for q, pts in zip(qs[1:], clouds[1:]):
         x = tr.step(pts)
         errs.append(float(np.abs(x[:nq] - q[:nq]).max()))
-    out = {"model": a.model, "points": a.points, "frames": a.frames - 1, "iters_per_frame": a.iters,
+        final_f.append(tr.cost.value_and_gradient(x)[0] / len(pts))  # (outside the frame's timing)
+    out = {"model": a.model, "points": a.points, "frames": a.frames - 1, "solver": a.solver,
+           "iters_per_frame": a.iters, "evaluations_per_frame": list(tr.iterations), "final_f_per_frame": final_f,
            "ms_per_iteration": tr.iteration_ms(), "ms_per_frame": float(np.mean(tr.frame_ms)),
            "set_points_ms": float(np.mean(tr.set_points_ms)),
            "point_evals_per_s_end_to_end": a.points * sum(tr.iterations) / (sum(tr.frame_ms) / 1e3),
