@@ -329,8 +329,50 @@ int fsdf_lm_minimize(fsdf_vgh_fn fn, void* user, int32_t n, double* x, int32_t i
  * fsdf_descend_lm: fsdf_lm_minimize over fsdf_value_gradient_hessian with
  * estimate_state's wrapped cost (src/tracking.jl:16-21): f = cost / n_points,
  * g = grad / n_points, H / n_points — fsdf_descend's sibling for the
- * second-order solver. A host loop: one synchronization per evaluation. x [nq]
- * is updated in place; outputs as fsdf_lm_minimize's. */
+ * second-order solver. By default a host loop, one synchronization per
+ * evaluation (fsdf_set_lm_solver: the device loop). x [nq] is updated in
+ * place; outputs as fsdf_lm_minimize's.
+ *
+ * fsdf_set_lm_prior: a prior on the frame's start state for fsdf_descend_lm.
+ * Gauss-Newton moves coordinates the cloud does not determine (a wrist joint
+ * under a noisy cloud: H_ii / N of 1e-5 .. 1e-9 against 1e-2 for the shoulder)
+ * by radians for a last 1e-6 of cost; with weights mu [nq], each >= 0, the
+ * objective of fsdf_descend_lm becomes
+ *     F(x) = c(x) / N + Σ_i mu_i (x_i − x̄_i)^2,
+ * x̄ the x handed to that call (the frame's warm start). One operation order,
+ * shared with flash.tracking.state_prior (the same bits): e_i = x_i − x̄_i;
+ * r = 0.0, r += mu_i * (e_i * e_i) in index order; f = c / N + r;
+ * g_i = g_i / N + (2.0 mu_i) e_i; H_ii = H_ii / N + 2.0 mu_i. weight NULL or
+ * n = 0 clears the prior (the default: fsdf_descend_lm is then exactly what it
+ * was, no zeros added); a negative or non-finite weight is FSDF_ERR_ARG; n
+ * other than nq is FSDF_ERR_STATE at the next fsdf_descend_lm;
+ * fsdf_set_mechanism clears it. Quaternion coordinates are penalised raw
+ * (un-normalised): a weight on a quaternion's four entries also fixes the
+ * quaternion's scale, which the cost itself leaves free. fsdf_lm_minimize and
+ * fsdf_lm_step know nothing of it: the prior is part of the objective.
+ *
+ * fsdf_set_lm_solver: where fsdf_descend_lm's loop runs. 0 (the default): the
+ * host loop above. 1: the device loop where the scene fits, the host loop
+ * otherwise. 2: the device loop is required — FSDF_ERR_STATE for a scene
+ * without resident points or whose solver kernels' work arrays do not fit
+ * their 64 KB of LDS (at most 64 joint coordinates; M64's 65 bodies, 48
+ * coordinates and 64 surfaces take 60 KB), FSDF_ERR_ARG for a damping that is
+ * not > 0 (mode 1 then takes the host loop: the device step's raises of a
+ * degenerate factorisation are bounded only from a positive damping). The
+ * device loop (csrc/solver.hip) enqueues the whole frame up front, as
+ * fsdf_descend's: FK of x and the first posed model, then per evaluation the
+ * pass with k* and ∇d* in resident order, its reduce, the moments and their
+ * reduce, one single-workgroup LM step — chain rule, the prior, accept or
+ * reject, on acceptance the Gauss-Newton matrix, the end conditions, the
+ * Cholesky step, the next trial — and the FK and pose of that trial; after the
+ * end the remaining launches return at once; x, value, count and damping are
+ * read back once. The arithmetic is the host loop's in its order
+ * (csrc/gn_impl.h, csrc/kin_impl.h): x, value, the evaluation count and the
+ * final damping are bit-identical to mode 0. A configuration whose poses are
+ * not finite fails the frame with FSDF_ERR_ARG (the host loop goes on with a
+ * NaN cost). */
+int fsdf_set_lm_prior(fsdf_ctx* ctx, const double* weight, int32_t n);
+int fsdf_set_lm_solver(fsdf_ctx* ctx, int32_t device_loop);
 int fsdf_eval_moments(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out, double* moments_out);
 int fsdf_value_gradient_hessian(fsdf_ctx* ctx, const double* x, double* cost_out, double* grad_out,
                                 double* hess_out);

@@ -305,6 +305,24 @@ function eval_moments(ctx::Context, poses::Vector{Float64})
     c[], accum, moments
 end
 
+"""
+The prior of fsdf_descend_lm on the frame's start state (fsdf_set_lm_prior): its
+objective becomes c/N + Σ weight[i] (x[i] − x̄[i])², x̄ the x handed to that call; one
+weight >= 0 per joint coordinate, quaternion coordinates penalised raw. An empty vector
+clears it.
+"""
+set_lm_prior!(ctx::Context, weight::Vector{Float64}) =
+    check(ctx.ptr, ccall((:fsdf_set_lm_prior, lib), Cint, (Ptr{Void}, Ptr{Float64}, Int32),
+                         ctx.ptr, weight, Int32(length(weight))), "set_lm_prior")
+
+"""
+Where fsdf_descend_lm's loop runs (fsdf_set_lm_solver): 0 the host loop (default), 1 the
+device loop where the scene fits, 2 the device loop required. The same bits.
+"""
+set_lm_solver!(ctx::Context, mode::Integer) =
+    check(ctx.ptr, ccall((:fsdf_set_lm_solver, lib), Cint, (Ptr{Void}, Int32), ctx.ptr, Int32(mode)),
+          "set_lm_solver")
+
 # Σ_p d*(p)² as a number of the state's type: the value from the pass; for a
 # Dual chunk, the first-order change of the cost through every surface pose
 # (δc = −(ω·(M − t×F) + δt·F) with ω = vee(δR Rᵀ)) and every RBF skin's

@@ -186,6 +186,8 @@ struct fsdf_ctx {
     std::vector<double> x_pass[2];
     int x_pass_next = 0;
   } mech;
+  int lm_solver_device = 0;          // fsdf_set_lm_solver: 0 host loop (default), 1 device where it fits, 2 required
+  std::vector<double> lm_prior;      // fsdf_set_lm_prior: fsdf_descend_lm's prior weights (empty: none)
   // device solver loop of fsdf_descend (solver.hip): the mechanism's device
   // arrays (built on the first device descend after fsdf_set_mechanism) and
   // one frame's state; pinned staging for x / divisors in and x, f, flags out
@@ -195,7 +197,7 @@ struct fsdf_ctx {
   bool solver_tree_ok = false;
   fsdf::SolverTree stree;
   fsdf::DevBuf<double> stree_blob;   // the tree blob (fsdf::SolverTree::blob)
-  fsdf::DevBuf<double> solver;       // x | div | Rb | tb | poses | f
+  fsdf::DevBuf<double> solver;       // x | div | Rb | tb | poses | f (descend_device), or descend_lm_device's state
   fsdf::DevBuf<int> solver_flags;
   fsdf::PinnedBuf<double> h_solver;  // pinned: x | div | f | flags (as doubles)
 };

@@ -258,8 +258,10 @@ bool moments_fit(int S);  // the scene's table fits kMomentsMaxLds
 size_t moments_partials_len(int64_t n, int S);
 // n > 0, moments_fit(S). d_pts: the resident cloud (precision 64 / 32; all
 // arithmetic fp64); d_moments [S][21]. A k* outside [0, S) contributes nothing.
+// skip (optional): a device flag; set, both launches return at once (the
+// evaluations a finished device LM frame still has queued, solver.hip)
 hipError_t launch_moments(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_grad, int64_t n,
-                          int S, double* d_partials, double* d_moments, hipStream_t s);
+                          int S, double* d_partials, double* d_moments, hipStream_t s, const int* skip = nullptr);
 
 hipError_t launch_to_f32(const double* src, float* dst, int64_t count, hipStream_t s);
 
@@ -373,6 +375,40 @@ hipError_t launch_solver_init(const SolverTree& T, const SolverState& st, const 
 hipError_t launch_solver_step(const SolverTree& T, const SolverState& st, const double* d_accum,
                               const LocalModel& lm, const PosedModel& pm, int precision, int it_before,
                               hipStream_t s);
+
+// ---- device Levenberg-Marquardt loop (solver.hip) ------------------------------
+// One frame's state of fsdf_descend_lm's device loop. The trial of evaluation k
+// (0-based; the frame's start x is trial 0) lies in slot k & 1 of x [2][nq],
+// its joint frames in slot k & 1 of Rb [2][12 nb] (as SolverState's); the
+// accepted point — xa, f, g [nq], H [nq][nq] — and the damping lam are apart
+// from them. flags [4] = (done: the skip flag of the frame's launches,
+// evaluations counted, error: 1 FK / chain rule / motion rows, 2 a non-finite
+// pose, unused). mu / x_ref [nq]: the prior's weights and reference
+// (fsdf_set_lm_prior), mu null: no prior.
+struct LmState {
+  double *x = nullptr, *Rb = nullptr;
+  double *xa = nullptr, *f = nullptr, *lam = nullptr, *g = nullptr, *H = nullptr;
+  const double *mu = nullptr, *x_ref = nullptr;
+  int* flags = nullptr;
+  double max_step = 0.0, tol = 0.0, n_points = 1.0, weight = 0.0;
+  int limit = 0;
+};
+// the LM step's LDS (its carve and the kernel's static __shared__) fits one
+// workgroup's 64 KB, and nq one wave (the factorisation owns a row per lane)
+bool lm_solver_fits(int nb, int nq, int S);
+// After evaluation it_before (0-based) — its pass, reduce and moments: the
+// trial's wrapped objective (+ prior), accept / reject, on acceptance the
+// Gauss-Newton matrix at the trial, the end conditions in the host loop's
+// order, the damped step (degenerate factorisations raise the damping inside
+// the launch) and the next trial into slot (it_before + 1) & 1. One workgroup.
+// x, f, the count and the damping equal fsdf_lm_minimize's bit for bit.
+hipError_t launch_lm_step(const SolverTree& T, const LmState& ls, const double* d_accum, const double* d_moments,
+                          int it_before, hipStream_t s);
+// FK of the trial in `slot`, its joint frames into that slot and the next
+// pass's posed model pm (solver_init_kernel's work for a later trial; skips
+// once flags[0] is set)
+hipError_t launch_lm_pose(const SolverTree& T, const LmState& ls, const LocalModel& lm, const PosedModel& pm,
+                          int precision, int slot, hipStream_t s);
 
 // Exchanged spatial shards (fsdf_set_points_keyed_device): the bounding box
 // (lo xyz, hi xyz; a device pointer into the scratch) of a device f64 cloud,

@@ -20,59 +20,12 @@
 #include <stdint.h>
 
 #include "flashsdf.h"
+#include "gn_impl.h"
 
-namespace {
-
-inline int joint_width(int kind) { return kind == 1 ? 1 : (kind == 2 ? 7 : 0); }
-
-// The motion rows of body b's joint, rows [width][6]: g_i = rows_i · (F, M) is
-// joint_gradient's entry i, the same expressions in the same order (revolute
-// ω = Rb·axis, v = tb × ω, row = −(v, ω); quaternion-floating: the four
-// rotation columns through E(q̂) with the normalization projection 1/|q| at
-// the caller's un-normalised q, then the translation columns −(Rb e_j, 0)).
-bool joint_rows(int kind, const double* a, const double* R, const double* o, const double* q, double* rows) {
-  if (kind == 1) {
-    double w[3], v[3];
-    for (int i = 0; i < 3; ++i) w[i] = R[3 * i] * a[0] + R[3 * i + 1] * a[1] + R[3 * i + 2] * a[2];
-    v[0] = o[1] * w[2] - o[2] * w[1];
-    v[1] = o[2] * w[0] - o[0] * w[2];
-    v[2] = o[0] * w[1] - o[1] * w[0];
-    for (int i = 0; i < 3; ++i) {
-      rows[i] = -v[i];
-      rows[3 + i] = -w[i];
-    }
-    return true;
-  }
-  if (kind != 2) return kind == 0;
-  const double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  if (!(nrm > 0)) return false;
-  const double W = q[0] / nrm, X = q[1] / nrm, Y = q[2] / nrm, Z = q[3] / nrm;
-  const double E[3][4] = {{-X, W, -Z, Y}, {-Y, Z, W, -X}, {-Z, -Y, X, W}};
-  double org[3];  // world origin of the frame after the joint
-  for (int i = 0; i < 3; ++i) org[i] = (R[3 * i] * q[4] + R[3 * i + 1] * q[5] + R[3 * i + 2] * q[6]) + o[i];
-  for (int j = 0; j < 4; ++j) {
-    double w[3], v[3];
-    for (int i = 0; i < 3; ++i)
-      w[i] = R[3 * i] * (2.0 * E[0][j]) + R[3 * i + 1] * (2.0 * E[1][j]) + R[3 * i + 2] * (2.0 * E[2][j]);
-    v[0] = org[1] * w[2] - org[2] * w[1];
-    v[1] = org[2] * w[0] - org[0] * w[2];
-    v[2] = org[0] * w[1] - org[1] * w[0];
-    for (int i = 0; i < 3; ++i) {
-      rows[6 * j + i] = -v[i] / nrm;
-      rows[6 * j + 3 + i] = -w[i] / nrm;
-    }
-  }
-  for (int j = 0; j < 3; ++j) {
-    double* r = rows + 6 * (4 + j);
-    r[0] = -R[j];
-    r[1] = -R[3 + j];
-    r[2] = -R[6 + j];
-    r[3] = r[4] = r[5] = 0.0;
-  }
-  return true;
-}
-
-}  // namespace
+// The per-element arithmetic is gn_impl.h's (the device LM loop, solver.hip,
+// runs the same functions in parallel): here the sequential loops over it.
+using fsdf::gn::joint_rows;
+using fsdf::gn::joint_width;
 
 extern "C" int fsdf_gauss_newton_matrix(int32_t nb, const int32_t* parent, const int32_t* kind, const int32_t* qoff,
                                         const double* axis, const double* Rb, const double* tb, const double* q,
@@ -117,18 +70,13 @@ extern "C" int fsdf_gauss_newton_matrix(int32_t nb, const int32_t* parent, const
       const int cj = qoff[b] + dj;
       const double* sj = rows + 6 * cj;
       double u[6];
-      for (int i = 0; i < 6; ++i) {
-        double s = 0.0;
-        for (int j = 0; j < 6; ++j) s += Cb[6 * i + j] * sj[j];
-        u[i] = s;
-      }
+      for (int i = 0; i < 6; ++i) u[i] = fsdf::gn::moment_row(Cb, sj, i);
       for (int a = b; a >= 1; a = parent[a]) {
         const int wa = a == b ? dj + 1 : joint_width(kind[a]);  // own joint: the upper triangle, mirrored
         for (int di = 0; di < wa; ++di) {
           const int ci = qoff[a] + di;
           const double* si = rows + 6 * ci;
-          double s = 0.0;
-          for (int j = 0; j < 6; ++j) s += si[j] * u[j];
+          const double s = fsdf::gn::row_dot(si, u);
           A_out[(size_t)ci * nq + cj] = s;
           A_out[(size_t)cj * nq + ci] = s;
         }
@@ -144,40 +92,34 @@ extern "C" int fsdf_lm_step(int32_t n, const double* H, const double* g, double 
   double* L = work;                    // [n][n], lower triangle
   double* y = work + (size_t)n * n;    // [n]
   double hmax = 0.0;
-  for (int i = 0; i < n; ++i)
-    if (H[(size_t)i * n + i] > hmax) hmax = H[(size_t)i * n + i];
+  for (int i = 0; i < n; ++i) hmax = fsdf::gn::diag_max(hmax, H[(size_t)i * n + i]);
   const double floor_d = 1e-12 * hmax;
   for (int j = 0; j < n; ++j) {
-    const double hjj = H[(size_t)j * n + j];
-    const double dj = hjj > floor_d ? hjj : floor_d;  // max(H_jj, 1e-12 max H) (a NaN H_jj meets the pivot test)
-    double p = hjj != hjj ? hjj : hjj + lambda * dj;
-    for (int k = 0; k < j; ++k) p -= L[(size_t)j * n + k] * L[(size_t)j * n + k];
-    if (!(p > 0.0) || !isfinite(p)) return FSDF_ERR_DEGENERATE;
+    // max(H_jj, 1e-12 max H) (a NaN H_jj meets the pivot test)
+    double p = fsdf::gn::damped_diagonal(H[(size_t)j * n + j], lambda, floor_d);
+    for (int k = 0; k < j; ++k) p = fsdf::gn::minus_product(p, L[(size_t)j * n + k], L[(size_t)j * n + k]);
+    if (fsdf::gn::bad_pivot(p)) return FSDF_ERR_DEGENERATE;
     const double ljj = sqrt(p);
     L[(size_t)j * n + j] = ljj;
     for (int i = j + 1; i < n; ++i) {
       double s = H[(size_t)i * n + j];
-      for (int k = 0; k < j; ++k) s -= L[(size_t)i * n + k] * L[(size_t)j * n + k];
+      for (int k = 0; k < j; ++k) s = fsdf::gn::minus_product(s, L[(size_t)i * n + k], L[(size_t)j * n + k]);
       L[(size_t)i * n + j] = s / ljj;
     }
   }
   for (int i = 0; i < n; ++i) {  // L y = g
     double s = g[i];
-    for (int k = 0; k < i; ++k) s -= L[(size_t)i * n + k] * y[k];
+    for (int k = 0; k < i; ++k) s = fsdf::gn::minus_product(s, L[(size_t)i * n + k], y[k]);
     y[i] = s / L[(size_t)i * n + i];
   }
   for (int i = n - 1; i >= 0; --i) {  // Lᵀ z = y
     double s = y[i];
-    for (int k = i + 1; k < n; ++k) s -= L[(size_t)k * n + i] * y[k];
+    for (int k = i + 1; k < n; ++k) s = fsdf::gn::minus_product(s, L[(size_t)k * n + i], y[k]);
     y[i] = s / L[(size_t)i * n + i];
   }
   for (int i = 0; i < n; ++i)
     if (!isfinite(y[i])) return FSDF_ERR_DEGENERATE;
-  for (int i = 0; i < n; ++i) {
-    const double s = -y[i];
-    const double lo = s < -max_step ? -max_step : s;
-    dx_out[i] = max_step < lo ? max_step : lo;
-  }
+  for (int i = 0; i < n; ++i) dx_out[i] = fsdf::gn::clamped_step(y[i], max_step);
   return FSDF_OK;
 }
 

@@ -2,8 +2,9 @@
 // centres and deformations, the host halves of one CostFunctor iteration
 // (FK, weight solve, chain rule) around a pass, the same with the Gauss-Newton
 // Hessian (fsdf_value_gradient_hessian) and its Levenberg-Marquardt loop
-// (fsdf_descend_lm), and the solver loops of fsdf_descend on the host and on
-// the device (solver.hip).
+// (fsdf_descend_lm, with the prior of fsdf_set_lm_prior, on the host or —
+// fsdf_set_lm_solver — on the device), and the solver loops of fsdf_descend on
+// the host and on the device (solver.hip).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -64,6 +65,7 @@ extern "C" int fsdf_set_mechanism(fsdf_ctx* c, int32_t nb, const int32_t* parent
   M.work.resize(6 * nb);
   M.rbf.clear();  // centre declarations name bodies of the previous tree
   M.x_prepared.clear();
+  c->lm_prior.clear();  // (weights per coordinate of the previous tree)
   c->solver_tree_ok = false;
   return FSDF_OK;
 }
@@ -334,25 +336,181 @@ extern "C" int fsdf_value_gradient_hessian(fsdf_ctx* c, const double* x, double*
 }
 
 // fsdf_lm_minimize (gauss_newton.cpp) over fsdf_value_gradient_hessian with
-// estimate_state's wrapped cost (c / n, ∂c/∂x / n, H / n): the host loop, one
-// synchronization per evaluation.
+// estimate_state's wrapped cost (c / n, ∂c/∂x / n, H / n) and, when one is set,
+// the prior on the frame's start state: the host loop, one synchronization
+// per evaluation.
 namespace {
 struct LmObjective {
   fsdf_ctx* c;
   int nq;
   double n_points;
+  const double* mu;     // fsdf_set_lm_prior's weights [nq], or null: no prior
+  const double* x_ref;  // the x handed to fsdf_descend_lm (the frame's warm start)
 };
 int lm_objective(void* user, const double* x, double* f, double* g, double* H) {
   const LmObjective& o = *(const LmObjective*)user;
   double cost = 0.0;
   const int rc = fsdf_value_gradient_hessian(o.c, x, &cost, g, H);
   if (rc) return rc;
-  *f = cost / o.n_points;
-  for (int i = 0; i < o.nq; ++i) g[i] = g[i] / o.n_points;
-  for (size_t i = 0; i < (size_t)o.nq * o.nq; ++i) H[i] = H[i] / o.n_points;
+  if (!o.mu) {
+    *f = cost / o.n_points;
+    for (int i = 0; i < o.nq; ++i) g[i] = g[i] / o.n_points;
+    for (size_t i = 0; i < (size_t)o.nq * o.nq; ++i) H[i] = H[i] / o.n_points;
+    return FSDF_OK;
+  }
+  // the prior Σ mu_i (x_i − x̄_i)^2 on the wrapped objective, in the one
+  // operation order flash.tracking.state_prior restates (the same bits)
+  double r = 0.0;
+  for (int i = 0; i < o.nq; ++i) {
+    const double e = x[i] - o.x_ref[i];
+    r += o.mu[i] * (e * e);
+    g[i] = g[i] / o.n_points + (2.0 * o.mu[i]) * e;
+  }
+  *f = cost / o.n_points + r;
+  for (int i = 0; i < o.nq; ++i)
+    for (int j = 0; j < o.nq; ++j) {
+      const size_t at = (size_t)i * o.nq + j;
+      H[at] = i == j ? H[at] / o.n_points + 2.0 * o.mu[i] : H[at] / o.n_points;
+    }
   return FSDF_OK;
 }
 }  // namespace
+
+extern "C" int fsdf_set_lm_prior(fsdf_ctx* c, const double* weight, int32_t n) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n < 0) return fail(c, FSDF_ERR_ARG, "set_lm_prior: n %d", n);
+  if (!weight || n == 0) {
+    c->lm_prior.clear();
+    return FSDF_OK;
+  }
+  for (int i = 0; i < n; ++i)
+    if (!(weight[i] >= 0.0) || !std::isfinite(weight[i]))
+      return fail(c, FSDF_ERR_ARG, "set_lm_prior: weight %d is negative or not finite", i);
+  c->lm_prior.assign(weight, weight + n);
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_lm_solver(fsdf_ctx* c, int32_t device_loop) {
+  if (!c) return FSDF_ERR_ARG;
+  if (device_loop < 0 || device_loop > 2) return fail(c, FSDF_ERR_ARG, "set_lm_solver: mode %d", device_loop);
+  c->lm_solver_device = device_loop;
+  return FSDF_OK;
+}
+
+static int build_solver_tree(fsdf_ctx* c);
+
+// fsdf_descend_lm with every evaluation on the device (solver.hip, "the device
+// Levenberg-Marquardt loop"): solver_init (FK of x -> the first posed model),
+// then per evaluation pass (k*, ∇d* in resident order) -> reduce -> moments ->
+// their reduce -> LM step -> FK + pose of the next trial, all enqueued up
+// front; one read-back of x, f, the count, the damping and the flags. The
+// same bits as fsdf_lm_minimize over lm_objective.
+// The rule of device_buffers.h, as run_pass_moments: (1) every buffer the
+// frame hands to a launch is reserved — per-point outputs, moments and their
+// partials, the solver state with the accepted g and H, the pinned staging;
+// (2) their pointers are read into locals; (3) the launches take the locals.
+// The cloud pointer alone is read again after the first evaluation's regroup,
+// which swaps the resident cloud's buffer (sort.hip regroup_points).
+static int descend_lm_device(fsdf_ctx* c, double* x, int32_t iteration_limit, double damping, double max_step,
+                             double tolerance, double n_points, double* value_out, int32_t* iterations_out,
+                             double* damping_out) {
+  auto& M = c->mech;
+  const int nq = M.nq, nb = M.nb, S = c->lm.S;
+  const int64_t n = c->n;
+  const bool prior = !c->lm_prior.empty();
+  const fsdf::SolverTree& T = c->stree;
+  if (damping_out) *damping_out = damping;  // (fsdf_lm_minimize's first line: also what a failed first evaluation leaves)
+  // device: x [2][nq] | x_ref [nq] | mu [nq] | lam | flags [4] (as 2 doubles) | f | xa [nq] | g [nq] |
+  // H [nq][nq] | Rb|tb [2][12 nb]; uploaded: the first 4 nq + 3, read back: lam | flags | f | xa
+  const size_t o_ref = 2 * (size_t)nq, o_mu = 3 * (size_t)nq, o_lam = 4 * (size_t)nq, o_flags = o_lam + 1,
+               o_f = o_flags + 2, o_xa = o_f + 1, o_g = o_xa + nq, o_H = o_g + nq, o_Rb = o_H + (size_t)nq * nq,
+               need = o_Rb + 24 * (size_t)nb;
+  const size_t up = o_f, back = (size_t)nq + 4;
+  // (1) reserve
+  int rc = ensure_outputs(c, n);
+  if (rc) return rc;
+  HIPCHECK(c, c->moments_partials.reserve(fsdf::moments_partials_len(n, S)));
+  HIPCHECK(c, c->moments.reserve((size_t)S * fsdf::kMomentsLen));
+  if (c->solver.capacity() < need) HIPCHECK(c, hipStreamSynchronize(c->stream));  // (an earlier frame's launches)
+  HIPCHECK(c, c->solver.reserve(need));
+  HIPCHECK(c, c->h_solver.reserve(up + back));
+  // (2) read the pointers
+  const void* d_pts = c->cur.pts.get();
+  int32_t* d_kstar = c->kstar.get();
+  double* d_grad = c->grad.get();
+  double* d_partials = c->moments_partials.get();
+  double* d_moments = c->moments.get();
+  double* d_accum = c->model.accum.get();
+  double* d = c->solver.get();
+  double* h = c->h_solver.get();
+  HIPCHECK(c, hipStreamSynchronize(c->stream));  // (the pinned staging of an earlier frame is free)
+  memset(h, 0, up * sizeof(double));
+  memcpy(h, x, (size_t)nq * sizeof(double));  // (trial 0)
+  memcpy(h + o_ref, x, (size_t)nq * sizeof(double));
+  if (prior) memcpy(h + o_mu, c->lm_prior.data(), (size_t)nq * sizeof(double));
+  h[o_lam] = damping;
+  fsdf::LmState ls;
+  ls.x = d;
+  ls.x_ref = d + o_ref;
+  ls.mu = prior ? d + o_mu : nullptr;
+  ls.lam = d + o_lam;
+  ls.flags = (int*)(d + o_flags);
+  ls.f = d + o_f;
+  ls.xa = d + o_xa;
+  ls.g = d + o_g;
+  ls.H = d + o_H;
+  ls.Rb = d + o_Rb;
+  ls.max_step = max_step;
+  ls.tol = tolerance;
+  ls.n_points = n_points;
+  ls.weight = M.weight;
+  ls.limit = iteration_limit;
+  fsdf::SolverState st;  // (solver_init's view: x0 in slot 0 -> Rb, tb and the first posed model)
+  st.x = ls.x;
+  st.Rb = ls.Rb;
+  st.f = ls.f;
+  st.flags = ls.flags;
+  // (3) enqueue
+  HIPCHECK(c, hipMemcpyAsync(d, h, up * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHECK(c, fsdf::launch_solver_init(T, st, c->lm, c->pm, c->precision, c->stream));
+  for (int it = 0; it < iteration_limit; ++it) {
+    rc = run_pass(c, nullptr, d_pts, n, d_accum, d_kstar, nullptr, d_grad, nullptr, true, true, ls.flags);
+    if (rc) return rc;
+    HIPCHECK(c, fsdf::launch_moments(c->precision, d_pts, d_kstar, d_grad, n, S, d_partials, d_moments, c->stream,
+                                     ls.flags));
+    if (it == 0) {  // (after the moments launch: they read the layout the pass ran on)
+      rc = iteration_regroup(c);
+      if (rc) return rc;
+      d_pts = c->cur.pts.get();
+    }
+    HIPCHECK(c, fsdf::launch_lm_step(T, ls, d_accum, d_moments, it, c->stream));
+    if (it + 1 < iteration_limit)
+      HIPCHECK(c, fsdf::launch_lm_pose(T, ls, c->lm, c->pm, c->precision, (it + 1) & 1, c->stream));
+  }
+  double* hb = h + up;  // lam | flags | f | xa
+  HIPCHECK(c, hipMemcpyAsync(hb, ls.lam, back * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  int flags[4];
+  memcpy(flags, hb + 1, sizeof flags);
+#if FSDF_SOLVER_TIMES
+  {
+    unsigned long long tt[16];
+    fsdf::solver_times(tt);
+    fprintf(stderr, "LM step phases of evaluation 5 (10 ns):");
+    for (int i = 1; i < 10; ++i) fprintf(stderr, " %lld", (long long)(tt[i] - tt[0]));
+    fprintf(stderr, "\n");
+  }
+#endif
+  if (iterations_out) *iterations_out = flags[1];
+  if (flags[1] > 0) {  // (as the host loop: x the last accepted point, also when a later evaluation failed)
+    memcpy(x, hb + 4, (size_t)nq * sizeof(double));
+    if (damping_out) *damping_out = hb[0];
+    if (value_out) *value_out = hb[3];
+  }
+  if (flags[2] == 2) return fail(c, FSDF_ERR_ARG, "descend_lm: poses not finite (configuration diverged)");
+  if (flags[2]) return fail(c, FSDF_ERR_ARG, "value_gradient_hessian: forward kinematics (bad configuration)");
+  return FSDF_OK;
+}
 
 extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, double damping, double max_step,
                                double tolerance, double n_points, double* value_out, int32_t* iterations_out,
@@ -364,8 +522,41 @@ extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, 
   if (c->mech.nb == 0) return fail(c, FSDF_ERR_STATE, "descend_lm: no mechanism (call fsdf_set_mechanism)");
   if (c->lm.R > 0 || c->mech.n_deform > 0)
     return fail(c, FSDF_ERR_STATE, "descend_lm: rigid scenes only (no RBF skin, no deformation)");
+  const auto& Mc = c->mech;
+  if ((int)Mc.surface_body.size() != c->lm.S || (int)Mc.poses.size() != 12 * c->lm.S)
+    return fail(c, FSDF_ERR_STATE,
+                "descend_lm: mechanism registered for another surface list (call fsdf_set_mechanism)");
   const int nq = c->mech.nq;
-  LmObjective o{c, nq, n_points};
+  const bool prior = !c->lm_prior.empty();
+  if (prior && (int)c->lm_prior.size() != nq)
+    return fail(c, FSDF_ERR_STATE, "descend_lm: the prior has %d weights, the mechanism %d coordinates",
+                (int)c->lm_prior.size(), nq);
+  // the device loop (fsdf_set_lm_solver 1 / 2): a finite damping > 0 (the
+  // step's raises of a degenerate factorisation are then bounded), resident
+  // points, the moments table and both solver kernels' carves within their LDS
+  if (c->lm_solver_device && iteration_limit > 0) {
+    const bool required = c->lm_solver_device == 2;
+    if (required && !(damping > 0.0))
+      return fail(c, FSDF_ERR_ARG, "descend_lm: the device loop needs a damping > 0");
+    bool device_loop = damping > 0.0 && c->n > 0 && fsdf::moments_fit(c->lm.S);
+    if (device_loop) {
+      HIPCHECK(c, hipSetDevice(c->device));
+      if (!c->solver_tree_ok) {
+        const int rc = build_solver_tree(c);
+        if (rc) return rc;
+      }
+      device_loop = fsdf::solver_fits(Mc.nb, nq, c->lm.S, c->stree.ni, c->stree.nd, 0, 0, nullptr) &&
+                    fsdf::lm_solver_fits(Mc.nb, nq, c->lm.S);
+    }
+    if (required && !device_loop)
+      return fail(c, FSDF_ERR_STATE, "descend_lm: the device loop was required (fsdf_set_lm_solver 2) but the scene %s",
+                  c->n == 0 ? "has no resident points" : "does not fit the solver kernels' LDS");
+    if (device_loop)
+      return descend_lm_device(c, x, iteration_limit, damping, max_step, tolerance, n_points, value_out,
+                               iterations_out, damping_out);
+  }
+  const std::vector<double> x_ref(x, x + (prior ? nq : 0));
+  LmObjective o{c, nq, n_points, prior ? c->lm_prior.data() : nullptr, prior ? x_ref.data() : nullptr};
   std::vector<double> work((size_t)3 * nq * nq + (size_t)5 * nq + 1);
   return fsdf_lm_minimize(lm_objective, &o, nq, x, iteration_limit, damping, max_step, tolerance, work.data(),
                           value_out, iterations_out, damping_out);

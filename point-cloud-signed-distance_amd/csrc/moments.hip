@@ -61,7 +61,9 @@ template <typename T>
 __global__ __launch_bounds__(kMomentsBlock) void moments_kernel(const T* __restrict__ pts,
                                                                 const int32_t* __restrict__ kstar,
                                                                 const double* __restrict__ grad, int64_t n, int S,
-                                                                int run, double* __restrict__ partials) {
+                                                                int run, double* __restrict__ partials,
+                                                                const int* __restrict__ skip) {
+  if (skip && *skip) return;  // (uniform: a finished device LM frame)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
   const int len = kMomentsLen * S;
   for (int t = tid; t < waves * len; t += blockDim.x) moments_tab[t] = 0.0;
@@ -137,21 +139,21 @@ __global__ __launch_bounds__(kMomentsBlock) void moments_kernel(const T* __restr
 }
 
 hipError_t launch_moments(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_grad, int64_t n,
-                          int S, double* d_partials, double* d_moments, hipStream_t s) {
+                          int S, double* d_partials, double* d_moments, hipStream_t s, const int* skip) {
   if (n <= 0 || !moments_fit(S) || !d_pts || !d_kstar || !d_grad || !d_partials || !d_moments)
     return hipErrorInvalidValue;
   const int groups = moments_groups(n), run = (int)moments_run(n), block = 64 * moments_waves(S);
   const size_t lds = (size_t)moments_waves(S) * S * kMomentsLen * sizeof(double);
   if (precision == 64)
     hipLaunchKernelGGL(moments_kernel<double>, dim3(groups), dim3(block), lds, s, (const double*)d_pts,
-                       d_kstar, d_grad, n, S, run, d_partials);
+                       d_kstar, d_grad, n, S, run, d_partials, skip);
   else
     hipLaunchKernelGGL(moments_kernel<float>, dim3(groups), dim3(block), lds, s, (const float*)d_pts, d_kstar,
-                       d_grad, n, S, run, d_partials);
+                       d_grad, n, S, run, d_partials, skip);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // the partials in workgroup order (the pass's tile reduce: fixed order)
-  return launch_reduce(d_partials, groups, kMomentsLen * S, d_moments, s);
+  return launch_reduce(d_partials, groups, kMomentsLen * S, d_moments, s, nullptr, nullptr, nullptr, skip);
 }
 
 }  // namespace fsdf

@@ -39,9 +39,13 @@
 // The pass / reduce / step launches of later iterations read `flags[0]`
 // (SolverState::flags) and return at once after convergence; the remaining
 // iterations of the frame cost their (empty) launches only.
+//
+// fsdf_descend_lm's device loop (fsdf_set_lm_solver) is at the end of this
+// file: lm_step_kernel and lm_pose_kernel.
 #include <hip/hip_runtime.h>
 
 #include "fsdf_internal.h"
+#include "gn_impl.h"
 #include "kin_impl.h"
 #include "pose_impl.h"
 #include "rbf_impl.h"
@@ -701,54 +705,13 @@ __device__ void publish(const SolverTree& T, const SolverState& st, const Lds& L
   }
 }
 
-template <typename TP, bool EXT>
-__global__ __launch_bounds__(kStepThreads) void solver_init_kernel(SolverTree T, SolverState st, LocalModel lm,
-                                                                   PosedModel pm) {
-  extern __shared__ double lds[];
-  __shared__ int bad, sing;
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    bad = 0;
-    sing = 0;
-  }
-  const Lds L = stage<kStepThreads, EXT>(T, st, lds, nullptr, 0);  // (x0 in slot 0)
-  __syncthreads();
-  fk<kStepThreads>(T, L, &bad);  // (ends with a barrier; the host zeroed the flags before this launch)
-  if (EXT && T.R > 0) rbf_prepare<kStepThreads>(T, L, &sing);  // (ends with a barrier)
-  publish<TP, kStepThreads, EXT>(T, st, L, true, bad, 0.0, 0, 0, lm, pm, EXT ? sing : 0);
-}
-
-// One step over NT threads (solver_step_kernel: kStepThreads). (A launch
-// that also did the pass's final reduce — its last workgroup running the step
-// — measured no faster: the hand-off between workgroups costs what the launch
-// saves; branch archive/fused-reduce-step, DESIGN.md §7 round 6.)
-template <typename TP, int NT, bool EXT>
-__device__ void step_body(const SolverTree& T, const SolverState& st, const double* __restrict__ accum,
-                          double* __restrict__ lds, const LocalModel& lm, const PosedModel& pm, int it_before) {
-  // (the frame's done flag loads with the stage's loads — thread 0's, into LDS:
-  // workgroup 0 of this launch may set the flag at its end, so two threads'
-  // own loads could disagree; after the stage's barrier the whole workgroup
-  // branches on the one value. A workgroup that reads it set returns — no
-  // pass follows a converged step)
-  __shared__ int bad, verdict, s_done, sing;
-  __shared__ double s_f, s_reg;
-  const int tid = threadIdx.x, nb = T.nb, nx = T.nx;
-  if (tid == 0) s_done = __builtin_nontemporal_load(st.flags);
-#if FSDF_SOLVER_TIMES
-  const int it0 = it_before;
-#endif
-  STAMP(0);
-  if (tid == 0) {
-    bad = 0;
-    if (EXT) sing = 0;
-  }
-  const Lds L = stage<NT, EXT>(T, st, lds, accum, it_before & 1);
-  if (EXT && T.R > 0) stage_rbf<NT>(T, st, L, it_before & 1);
-  __syncthreads();
-  if (s_done) return;  // converged (or failed): the frame's remaining steps are no-ops (workgroup-uniform)
-  STAMP(1);
-  const bool skins = EXT && T.R > 0;
-  if (EXT) rbf_adjoint<NT>(T, st, L, &s_reg);  // (ends with a barrier)
+// The chain rule's subtree wrenches: per body its surfaces' accumulator rows in
+// index order (from the RBF chain's body wrench with skins), then the subtree
+// sums, children in descending index — fsdf_config_gradient's additions in its
+// order — into L.sub [nb][6]. Ends with a barrier.
+template <int NT>
+__device__ void subtree_wrenches(const SolverTree& T, const Lds& L, bool skins) {
+  const int tid = threadIdx.x, nb = T.nb;
   if (T.chains) {
     // chains (every non-root body has <= 1 child): body b's subtree sum along
     // its chain, deepest first — sub[a] = own[a] + sub[child], own[a] the body's
@@ -822,6 +785,57 @@ __device__ void step_body(const SolverTree& T, const SolverState& st, const doub
       }
     }
   }
+}
+
+template <typename TP, bool EXT>
+__global__ __launch_bounds__(kStepThreads) void solver_init_kernel(SolverTree T, SolverState st, LocalModel lm,
+                                                                   PosedModel pm) {
+  extern __shared__ double lds[];
+  __shared__ int bad, sing;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    bad = 0;
+    sing = 0;
+  }
+  const Lds L = stage<kStepThreads, EXT>(T, st, lds, nullptr, 0);  // (x0 in slot 0)
+  __syncthreads();
+  fk<kStepThreads>(T, L, &bad);  // (ends with a barrier; the host zeroed the flags before this launch)
+  if (EXT && T.R > 0) rbf_prepare<kStepThreads>(T, L, &sing);  // (ends with a barrier)
+  publish<TP, kStepThreads, EXT>(T, st, L, true, bad, 0.0, 0, 0, lm, pm, EXT ? sing : 0);
+}
+
+// One step over NT threads (solver_step_kernel: kStepThreads). (A launch
+// that also did the pass's final reduce — its last workgroup running the step
+// — measured no faster: the hand-off between workgroups costs what the launch
+// saves; branch archive/fused-reduce-step, DESIGN.md §7 round 6.)
+template <typename TP, int NT, bool EXT>
+__device__ void step_body(const SolverTree& T, const SolverState& st, const double* __restrict__ accum,
+                          double* __restrict__ lds, const LocalModel& lm, const PosedModel& pm, int it_before) {
+  // (the frame's done flag loads with the stage's loads — thread 0's, into LDS:
+  // workgroup 0 of this launch may set the flag at its end, so two threads'
+  // own loads could disagree; after the stage's barrier the whole workgroup
+  // branches on the one value. A workgroup that reads it set returns — no
+  // pass follows a converged step)
+  __shared__ int bad, verdict, s_done, sing;
+  __shared__ double s_f, s_reg;
+  const int tid = threadIdx.x, nb = T.nb, nx = T.nx;
+  if (tid == 0) s_done = __builtin_nontemporal_load(st.flags);
+#if FSDF_SOLVER_TIMES
+  const int it0 = it_before;
+#endif
+  STAMP(0);
+  if (tid == 0) {
+    bad = 0;
+    if (EXT) sing = 0;
+  }
+  const Lds L = stage<NT, EXT>(T, st, lds, accum, it_before & 1);
+  if (EXT && T.R > 0) stage_rbf<NT>(T, st, L, it_before & 1);
+  __syncthreads();
+  if (s_done) return;  // converged (or failed): the frame's remaining steps are no-ops (workgroup-uniform)
+  STAMP(1);
+  const bool skins = EXT && T.R > 0;
+  if (EXT) rbf_adjoint<NT>(T, st, L, &s_reg);  // (ends with a barrier)
+  subtree_wrenches<NT>(T, L, skins);  // (ends with a barrier)
   STAMP(2);
   for (int b = 1 + tid; b < nb; b += NT) {
     const int k = L.kind[b];
@@ -888,6 +902,406 @@ __global__ __launch_bounds__(kStepThreads) void solver_step_kernel(SolverTree T,
                                                                    PosedModel pm, int it_before) {
   extern __shared__ double lds[];
   step_body<TP, kStepThreads, EXT>(T, st, accum, lds, lm, pm, it_before);
+}
+
+// ---- the device Levenberg-Marquardt loop (fsdf_descend_lm, fsdf_set_lm_solver) ----
+// After every evaluation (pass, reduce, moments, their reduce) one single-
+// workgroup launch, lm_step_kernel, does what fsdf_lm_minimize does between two
+// calls of its objective, in the host's order and with gn_impl.h's arithmetic:
+//   objective   the chain rule of step_body; f_t = c / N, g / N (+ the prior of
+//               fsdf_set_lm_prior, iterate.hip lm_objective's operations)
+//   verdict     the first evaluation is accepted, a later one when f_t < f; on
+//               acceptance the Gauss-Newton matrix at the trial (per-body
+//               moments in surface order, subtree sums by height with the
+//               children in descending index, u = C_b s_j, one thread per
+//               matrix entry), H = (2 A) / N (+ prior), and x, f, g, H kept as
+//               the accepted state in global memory; lambda / 10 (>= 1e-12),
+//               or x 10 and the end beyond 1e12 on rejection
+//   end         the evaluation count, then |g|_2 of the accepted point summed
+//               in index order
+//   step        fsdf_lm_step in wave 0, a matrix row per lane: left-looking
+//               Cholesky (every L_ij subtracts L_ik L_jk for k ascending), the
+//               forward solve column by column, the back-substitution's
+//               products in the lanes and added in ascending k (readlane); a
+//               degenerate factorisation raises lambda and factors again
+//   next trial  x + step into the other slot
+// and a second launch, lm_pose_kernel (solver_init_kernel's work on that slot:
+// FK, the joint frames, the posed model), prepares the next pass. The solve in
+// a launch of one workgroup keeps the matrix, the factor and the subtree
+// moments out of the many-workgroup pose launch, whose carve (the tree blob in
+// LDS) fills most of 64 KB at M64; here the tree is read from global memory
+// (L2) and the carve is acc | Rb tb | x | own | sub | g | xa | pe | C [nb][36] |
+// rows [nq][6] | u [nq][6] | L [nq][nq | 1] | the coordinates' bodies | the parents: 60 KB at
+// M64 (65 bodies, 48 coordinates, 64 surfaces).
+constexpr int kLmThreads = 1024;
+constexpr int kLmMaxRaises = 400;  // tenfold raises from the smallest positive double pass 1e12 in 336
+
+__host__ __device__ inline int lm_ld(int nq) { return nq | 1; }  // (odd row stride: the lanes' rows in different banks)
+__host__ __device__ inline size_t lm_work_doubles(int nb, int nq, int S) {
+  return (1 + 6 * (size_t)S) + 60 * (size_t)nb + 16 * (size_t)nq + (size_t)nq * lm_ld(nq) + ((size_t)nq + (size_t)nb + 1) / 2;
+}
+
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// fsdf_lm_step by one wave, lane i owning row i (n <= 64): A [n][ld] in LDS
+// holds H (its lower triangle is read) and becomes the factor; hd = this
+// lane's H_ii, g its gradient entry. false: a degenerate factorisation or a
+// solve that is not finite. *step = this lane's clamped step entry.
+__device__ bool lm_wave_step(int n, int ld, double* A, double hd, double g, double lambda, double floor_d,
+                             double max_step, double* step, int it0 = -1) {
+  (void)it0;  // (FSDF_SOLVER_TIMES: the evaluation whose phases are clocked)
+  const int lane = threadIdx.x & 63;
+  const bool in = lane < n;
+  double* row = A + (in ? lane : 0) * ld;
+  for (int j = 0; j < n; ++j) {
+    double s = 0.0;
+    if (in && lane >= j) {
+      s = lane == j ? gn::damped_diagonal(hd, lambda, floor_d) : row[j];
+      const double* rj = A + j * ld;
+      // (eight terms' loads before their subtractions: the chain then waits for one LDS latency
+      // per eight terms, not per term — the order of the subtractions is unchanged)
+      int k = 0;
+      for (; k + 8 <= j; k += 8) {
+        double a[8], b[8];
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+          a[v] = row[k + v];
+          b[v] = rj[k + v];
+        }
+#pragma unroll
+        for (int v = 0; v < 8; ++v) s = gn::minus_product(s, a[v], b[v]);
+      }
+      for (; k < j; ++k) s = gn::minus_product(s, row[k], rj[k]);
+    }
+    const double p = readlane_f64(s, j);
+    if (gn::bad_pivot(p)) return false;
+    const double ljj = sqrt(p);
+    if (in && lane >= j) row[j] = lane == j ? ljj : s / ljj;
+    wave_lds_fence();
+  }
+  STAMP(6);
+  double y = in ? g : 0.0;
+  for (int k = 0; k < n; ++k) {  // L y = g, column by column: every row's terms in ascending k
+    const double lkk = A[k * ld + k];
+    if (lane == k) y = y / lkk;
+    const double yk = readlane_f64(y, k);
+    if (in && lane > k) y = gn::minus_product(y, row[k], yk);
+  }
+  STAMP(7);
+  for (int i = n - 1; i >= 0; --i) {  // Lᵀ z = y: the products in the lanes k > i, subtracted in ascending k
+    const double p = in && lane > i ? row[i] * y : 0.0;
+    double s = readlane_f64(y, i);
+    for (int k = i + 1; k < n; ++k) s = s - readlane_f64(p, k);
+    s = s / A[i * ld + i];
+    if (lane == i) y = s;
+  }
+  STAMP(8);
+  if (__builtin_amdgcn_ballot_w64(in && !isfinite(y)) != 0) return false;
+  *step = gn::clamped_step(y, max_step);
+  return true;
+}
+
+__global__ __launch_bounds__(kLmThreads) void lm_step_kernel(SolverTree T, LmState ls,
+                                                             const double* __restrict__ accum,
+                                                             const double* __restrict__ moments, int it_before) {
+  extern __shared__ double lds[];
+  constexpr int NT = kLmThreads;
+  // (bad: the chain rule's failures, read by every thread before the matrix phase; bad_rows: that phase's own)
+  __shared__ int s_done, bad, bad_rows, s_accept, s_end;
+  __shared__ double s_f, s_lam;
+  const int tid = threadIdx.x, nb = T.nb, nq = T.nq, S = T.S, ld = lm_ld(nq);
+#if FSDF_SOLVER_TIMES
+  const int it0 = it_before;  // (phases, 10 ns: 1 staged, 2 chain rule, 3 verdict, 4 matrix, 5 end checks,
+                              // 6 factor, 7 forward solve, 8 back-substitution, 9 end)
+#else
+  const int it0 = -1;
+#endif
+  STAMP(0);
+  if (tid == 0) {
+    s_done = __builtin_nontemporal_load(ls.flags);
+    bad = 0;
+    bad_rows = 0;
+  }
+  // the tree from global memory; the work arrays in LDS
+  const double* bd = (const double*)T.blob;
+  const int32_t* bi = (const int32_t*)(bd + T.nd);
+  Lds L = {};
+  L.axis = bd + T.axis;
+  L.parent = bi + T.parent;
+  L.kind = bi + T.kind;
+  L.qoff = bi + T.qoff;
+  L.hord = bi + T.height_order;
+  L.hoff = bi + T.height_off;
+  L.coff = bi + T.child_off;
+  L.clist = bi + T.child_list;
+  L.soff = bi + T.surf_off;
+  L.slist = bi + T.surf_list;
+  L.chlist = bi + T.chain_list;
+  L.choff = bi + T.chain_off;
+  double* d = lds;
+  const int na = 1 + 6 * S, nr = 12 * nb;
+  L.acc = d;
+  d += na;
+  L.Rb = d;
+  d += 9 * nb;
+  L.tb = d;
+  d += 3 * nb;
+  L.x = d;
+  d += nq;
+  L.LR = d;  // (subtree_wrenches' own [nb][6])
+  d += 6 * nb;
+  L.sub = d;
+  d += 6 * nb;
+  L.g = d;
+  d += nq;
+  double* xa = d;  // the accepted x
+  d += nq;
+  double* pe = d;  // the prior's terms mu_i e_i^2
+  d += nq;
+  double* C = d;  // [nb][36] subtree moments
+  d += 36 * nb;
+  double* rows = d;  // [nq][6] motion rows
+  d += 6 * nq;
+  double* u = d;  // [nq][6] C_b s_j
+  d += 6 * nq;
+  double* A = d;  // [nq][ld] H, then its factor
+  d += nq * ld;
+  int32_t* cbody = (int32_t*)d;  // [nq] the body whose joint owns the coordinate (-1: none)
+  int32_t* par = cbody + nq;     // [nb] the tree's parents (the matrix entries' ancestor walks)
+  // stage: every thread's loads before its first store (stage()); na <= NT, nr <= 2 NT, nq <= 64 (lm_solver_fits)
+  const int slot = it_before & 1;
+  const double* rsrc = ls.Rb + (size_t)slot * nr;
+  const bool mine = tid < nq, later = it_before > 0;
+  const double a0 = tid < na ? accum[tid] : 0.0;
+  const double r0 = tid < nr ? rsrc[tid] : 0.0, r1 = tid + NT < nr ? rsrc[tid + NT] : 0.0;
+  const double x0 = mine ? ls.x[(size_t)slot * nq + tid] : 0.0;
+  const double xa0 = mine && later ? ls.xa[tid] : 0.0, ga0 = mine && later ? ls.g[tid] : 0.0;
+  const double mu0 = mine && ls.mu ? ls.mu[tid] : 0.0, xr0 = mine && ls.mu ? ls.x_ref[tid] : 0.0;
+  double h_old[(64 * 64 + NT - 1) / NT];  // (a rejected trial: the accepted H into the factor's place)
+#pragma unroll
+  for (int v = 0; v < (64 * 64 + NT - 1) / NT; ++v) {
+    const int i = tid + v * NT;
+    h_old[v] = later && i < nq * nq ? ls.H[i] : 0.0;
+  }
+  if (tid < na) L.acc[tid] = a0;
+  if (tid < nr) L.Rb[tid] = r0;  // (Rb | tb adjacent, as in a slot)
+  if (tid + NT < nr) L.Rb[tid + NT] = r1;
+  if (mine) {
+    L.x[tid] = x0;
+    L.g[tid] = 0.0;
+    cbody[tid] = -1;
+    const double e = x0 - xr0;
+    pe[tid] = mu0 * (e * e);
+  }
+  for (int i = tid; i < 6 * nq; i += NT) rows[i] = 0.0;
+  for (int i = tid; i < nb; i += NT) par[i] = L.parent[i];
+  __syncthreads();
+  if (s_done) return;  // the frame has ended: its remaining launches are no-ops (workgroup-uniform)
+  STAMP(1);
+  // the chain rule (step_body's)
+  subtree_wrenches<NT>(T, L, false);  // (ends with a barrier)
+  for (int b = 1 + tid; b < nb; b += NT) {
+    const int k = L.kind[b];
+    if (k && !kin::joint_gradient(k, L.axis + 3 * b, L.Rb + 9 * b, L.tb + 3 * b, L.x + L.qoff[b], L.sub + 6 * b,
+                                  L.g + L.qoff[b]))
+      atomicOr(&bad, 1);
+  }
+  __syncthreads();
+  STAMP(2);
+  // the wrapped objective at the trial (iterate.hip lm_objective) and the verdict
+  if (mine) {
+    double gi = L.g[tid] / ls.n_points;
+    if (ls.mu) gi = gi + (2.0 * mu0) * (x0 - xr0);
+    L.g[tid] = gi;
+  }
+  if (tid == 0) {
+    const double cost = L.acc[0] + ls.weight * 0.0;  // (iteration_finish: the regularizer's sum is 0.0)
+    double ft = cost / ls.n_points;
+    if (ls.mu) {
+      double r = 0.0;
+      for (int i = 0; i < nq; ++i) r += pe[i];
+      ft = ft + r;
+    }
+    const double f = later ? *ls.f : ft;
+    double lam = *ls.lam;
+    const bool accept = !later || ft < f;
+    int end = 0;
+    if (accept) {
+      if (later) lam = 1e-12 > lam / 10.0 ? 1e-12 : lam / 10.0;
+    } else {
+      lam *= 10.0;
+      if (lam > 1e12) end = 1;
+    }
+    s_f = accept ? ft : f;
+    s_lam = lam;
+    s_accept = accept;
+    s_end = end;
+  }
+  __syncthreads();
+  STAMP(3);
+  const int count = it_before + 1;
+  const bool accept = s_accept != 0, last = count >= ls.limit;
+  if (accept && !last && !bad) {
+    // the Gauss-Newton matrix at the trial (fsdf_gauss_newton_matrix): per-body
+    // moments, surfaces in index order; the motion rows
+    for (int i = tid; i < 36 * (nb - 1); i += NT) {
+      const int b = 1 + i / 36, e = i % 36, t = gn::tri_index(e / 6, e % 6);
+      double s = 0.0;
+      for (int q = L.soff[b]; q < L.soff[b + 1]; ++q) s += moments[kMomentsLen * L.slist[q] + t];
+      C[36 * b + e] = s;
+    }
+    for (int b = 1 + tid; b < nb; b += NT) {
+      const int k = L.kind[b], w = gn::joint_width(k), q0 = L.qoff[b];
+      if (!w) continue;
+      if (!gn::joint_rows(k, L.axis + 3 * b, L.Rb + 9 * b, L.tb + 3 * b, L.x + q0, rows + 6 * q0))
+        atomicOr(&bad_rows, 1);
+      for (int e = 0; e < w; ++e) cbody[q0 + e] = b;
+    }
+    __syncthreads();
+    // subtree sums: parents by height, children in descending index
+    for (int h = 0; h < T.H; ++h) {
+      const int a = L.hoff[h], e = L.hoff[h + 1];
+      for (int i = tid; i < 36 * (e - a); i += NT) {
+        const int p = L.hord[a + i / 36], j = i % 36;
+        double s = C[36 * p + j];
+        for (int q = L.coff[p]; q < L.coff[p + 1]; ++q) s += C[36 * L.clist[q] + j];
+        C[36 * p + j] = s;
+      }
+      __syncthreads();
+    }
+    for (int i = tid; i < 6 * nq; i += NT) {
+      const int c = i / 6, b = cbody[c];
+      u[i] = b > 0 ? gn::moment_row(C + 36 * b, rows + 6 * c, i % 6) : 0.0;
+    }
+    __syncthreads();
+    // one entry per thread: coordinate i against j when i's body is j's, or
+    // an ancestor of it (a parent's index is below its child's)
+    for (int i = tid; i < nq * nq; i += NT) {
+      const int r = i / nq, c = i % nq, br = cbody[r], bc = cbody[c];
+      double a = 0.0;
+      if (br > 0 && bc > 0) {
+        if (br == bc) {
+          a = gn::row_dot(rows + 6 * (r < c ? r : c), u + 6 * (r < c ? c : r));
+        } else {
+          const int deep = br > bc ? br : bc, top = br > bc ? bc : br;
+          int t = deep;
+          while (t > top) t = par[t];
+          if (t == top) a = gn::row_dot(rows + 6 * (br > bc ? c : r), u + 6 * (br > bc ? r : c));
+        }
+      }
+      double h = (2.0 * a) / ls.n_points;
+      if (ls.mu && r == c) h = h + 2.0 * ls.mu[r];
+      ls.H[i] = h;
+      A[r * ld + c] = h;
+    }
+  } else if (!accept) {
+#pragma unroll
+    for (int v = 0; v < (64 * 64 + NT - 1) / NT; ++v) {
+      const int i = tid + v * NT;
+      if (i < nq * nq) A[(i / nq) * ld + i % nq] = h_old[v];
+    }
+  }
+  if (mine) {  // (the accepted point, for the step)
+    xa[tid] = accept ? x0 : xa0;
+    if (!accept) L.g[tid] = ga0;
+  }
+  __syncthreads();
+  if (bad || bad_rows) {  // (the evaluation failed: not counted, the accepted state as it was — the host's)
+    if (tid == 0) {
+      ls.flags[2] = 1;
+      ls.flags[0] = 1;
+    }
+    return;
+  }
+  if (tid >= 64) return;
+  STAMP(4);
+  if (mine && accept) {
+    ls.xa[tid] = x0;
+    ls.g[tid] = L.g[tid];
+  }
+  // wave 0: the end conditions in fsdf_lm_minimize's order, then the damped step
+  const int lane = tid;
+  const double gi = mine ? L.g[lane] : 0.0;
+  double lam = s_lam, step = 0.0;
+  int done = s_end || last;
+  if (!done) {
+    const double sq = gi * gi;
+    double nrm2 = 0.0;
+    for (int i = 0; i < nq; ++i) nrm2 += readlane_f64(sq, i);
+    if (sqrt(nrm2) < ls.tol) done = 1;
+  }
+  if (!done) {
+    const double hd = mine ? A[lane * ld + lane] : 0.0;
+    double hmax = 0.0;
+    for (int i = 0; i < nq; ++i) hmax = gn::diag_max(hmax, readlane_f64(hd, i));
+    const double floor_d = 1e-12 * hmax;
+    STAMP(5);
+    for (int raises = 0;; ++raises) {  // (bounded: lambda grows tenfold every turn)
+      if (raises > 0) {  // the factor's place holds a failed factorisation: H again
+        for (int i = lane; i < nq * nq; i += 64) A[(i / nq) * ld + i % nq] = ls.H[i];
+        wave_lds_fence();
+      }
+      if (lm_wave_step(nq, ld, A, hd, gi, lam, floor_d, ls.max_step, &step, it0)) break;
+      lam *= 10.0;
+      if (lam > 1e12 || raises >= kLmMaxRaises) {
+        done = 1;
+        break;
+      }
+    }
+  }
+  if (!done && mine) ls.x[(size_t)(count & 1) * nq + lane] = xa[lane] + step;
+  if (lane == 0) {
+    *ls.lam = lam;
+    if (accept) *ls.f = s_f;
+    ls.flags[1] = count;
+    if (done) ls.flags[0] = 1;
+  }
+  STAMP(9);
+}
+
+// solver_init_kernel's work for a later trial of the LM frame: FK of the x in
+// `slot`, the surface poses, this workgroup's pose items, and — workgroup 0 —
+// the joint frames into the slot and the error flags (publish()'s, without the
+// NaiveSolver's x, f and count).
+template <typename TP>
+__global__ __launch_bounds__(kStepThreads) void lm_pose_kernel(SolverTree T, SolverState st, LocalModel lm,
+                                                               PosedModel pm, int slot) {
+  extern __shared__ double lds[];
+  constexpr int NT = kStepThreads;
+  __shared__ int bad, s_done, nonfinite;
+  const int tid = threadIdx.x, nb = T.nb;
+  if (tid == 0) {
+    s_done = __builtin_nontemporal_load(st.flags);
+    bad = 0;
+    nonfinite = 0;
+  }
+  const Lds L = stage<NT, false>(T, st, lds, nullptr, slot);
+  __syncthreads();
+  if (s_done) return;
+  fk<NT>(T, L, &bad);  // (ends with a barrier)
+  for (int i = tid; i < 12 * T.S; i += NT) {
+    const int k = i / 12, q = i % 12, b = L.sbody[k];
+    const double v = b < 0 ? ((q % 4 == 0 && q < 9) ? 1.0 : 0.0)
+                           : kin::surface_pose_entry(q, L.R + 9 * b, L.t + 3 * b, L.FR + 9 * k, L.Ft + 3 * k);
+    L.P[i] = v;
+    if (!isfinite(v)) nonfinite = 1;  // (every writer writes the same value)
+  }
+  __syncthreads();
+  const int item = blockIdx.x * NT + tid;
+  if (item < pose_items(lm))
+    pose_item<TP>(lm, L.P, (TP*)pm.planes_w, pm.spheres_w, (TP*)pm.verts_w, (TP*)pm.hscale_w,
+                  sizeof(TP) == 8 ? pm.screen_w : nullptr, sizeof(TP) == 8 ? (I4*)pm.image_w : nullptr, item);
+  if (blockIdx.x != 0) return;
+  double* Rb = st.Rb + (size_t)slot * 12 * nb;
+  for (int i = tid; i < 9 * nb; i += NT) Rb[i] = L.Rb[i];
+  for (int i = tid; i < 3 * nb; i += NT) Rb[9 * nb + i] = L.tb[i];
+  if (tid == 0 && (bad || nonfinite)) {
+    st.flags[2] = nonfinite ? 2 : 1;
+    st.flags[0] = 1;
+  }
 }
 
 bool extended(const SolverTree& T) { return T.R > 0 || T.n_deform > 0; }
@@ -993,6 +1407,41 @@ hipError_t launch_solver_step(const SolverTree& T, const SolverState& st, const 
       hipLaunchKernelGGL((solver_step_kernel<double, false>), g, b, lds, s, T, st, d_accum, lm, pm, it_before);
     else hipLaunchKernelGGL((solver_step_kernel<float, false>), g, b, lds, s, T, st, d_accum, lm, pm, it_before);
   }
+  return hipGetLastError();
+}
+
+// the LM step's carve with lm_step_kernel's static __shared__ within 64 KB; a
+// matrix row per lane of one wave; the staging's loads per thread
+bool lm_solver_fits(int nb, int nq, int S) {
+  static size_t fixed = 0;
+  static bool known = false;
+  if (!known) {
+    hipFuncAttributes a;
+    // (a failed query: an allowance above what the kernel declares today)
+    fixed = hipFuncGetAttributes(&a, (const void*)lm_step_kernel) == hipSuccess ? a.sharedSizeBytes : 256;
+    known = true;
+  }
+  return nb >= 1 && nq >= 1 && nq <= 64 && 1 + 6 * (size_t)S <= (size_t)kLmThreads &&
+         12 * (size_t)nb <= 2 * (size_t)kLmThreads && lm_work_doubles(nb, nq, S) * 8 + fixed <= 65536;
+}
+
+hipError_t launch_lm_step(const SolverTree& T, const LmState& ls, const double* d_accum, const double* d_moments,
+                          int it_before, hipStream_t s) {
+  hipLaunchKernelGGL(lm_step_kernel, dim3(1), dim3(kLmThreads), lm_work_doubles(T.nb, T.nq, T.S) * sizeof(double), s,
+                     T, ls, d_accum, d_moments, it_before);
+  return hipGetLastError();
+}
+
+hipError_t launch_lm_pose(const SolverTree& T, const LmState& ls, const LocalModel& lm, const PosedModel& pm,
+                          int precision, int slot, hipStream_t s) {
+  SolverState st;
+  st.x = ls.x;
+  st.Rb = ls.Rb;
+  st.flags = ls.flags;
+  const dim3 g = solver_grid(lm), b(kStepThreads);
+  const size_t lds = solver_lds_bytes(T);
+  if (precision == 64) hipLaunchKernelGGL(lm_pose_kernel<double>, g, b, lds, s, T, st, lm, pm, slot);
+  else hipLaunchKernelGGL(lm_pose_kernel<float>, g, b, lds, s, T, st, lm, pm, slot);
   return hipGetLastError();
 }
 

@@ -113,6 +113,8 @@ _PROTOS = {
     "fsdf_value_gradient_hessian": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
     "fsdf_descend_lm": (c_int32, [c_void_p, c_void_p, c_int32, c_double, c_double, c_double, c_double,
                                   POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
+    "fsdf_set_lm_prior": (c_int32, [c_void_p, c_void_p, c_int32]),
+    "fsdf_set_lm_solver": (c_int32, [c_void_p, c_int32]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -605,6 +607,32 @@ class Context:
                                         float(tolerance), float(n_points), ctypes.byref(f), ctypes.byref(it),
                                         ctypes.byref(lam)), self._ctx, "descend_lm")
         return x, f.value, it.value, lam.value
+
+    def set_lm_prior(self, weight):
+        """fsdf_set_lm_prior: descend_lm's objective becomes c/N + Σ weight_i
+        (x_i − x̄_i)², x̄ the x handed to that call. weight: one value per
+        joint coordinate (a scalar is repeated), each >= 0; None clears it."""
+        if weight is None:
+            check(self._lib.fsdf_set_lm_prior(self._ctx, None, 0), self._ctx, "set_lm_prior")
+            return
+        w = np.asarray(weight, np.float64)
+        if w.ndim == 0:
+            if not hasattr(self, "nq"):
+                raise ValueError("set_lm_prior: a scalar weight needs the mechanism's coordinate count "
+                                 "(call set_mechanism first)")
+            w = np.full(self.nq, float(w))
+        w = np.ascontiguousarray(w).reshape(-1)
+        check(self._lib.fsdf_set_lm_prior(self._ctx, ptr(w), w.size), self._ctx, "set_lm_prior")
+
+    def set_lm_solver(self, device_loop):
+        """fsdf_set_lm_solver: descend_lm's loop on the host (False / 0, the
+        default), on the device where the scene fits (True / 1), or required
+        there ("require" / 2: FSDF_ERR_STATE otherwise). The same bits."""
+        mode = {"require": 2}.get(device_loop) if isinstance(device_loop, str) else int(device_loop)
+        if mode is None:
+            raise ValueError(f"set_lm_solver: unknown mode {device_loop!r}")
+        check(self._lib.fsdf_set_lm_solver(self._ctx, mode), self._ctx, "set_lm_solver")
+        self.lm_solver_mode = mode  # (the library keeps no getter: callers that switch for one call restore this)
 
     def descend(self, x, iteration_limit, rate, max_step, tolerance=0.0, divisors=None, n_points=1.0):
         """fsdf_descend: the NaiveSolver loop over value_and_gradient natively.

@@ -218,12 +218,31 @@ class CostFunctor:
         self._native_rigid("value_gradient_hessian")
         return self.ctx.value_gradient_hessian(np.asarray(x, np.float64))
 
-    def descend_lm(self, x, iteration_limit, damping, max_step, tolerance=0.0, n_points=1.0):
+    def descend_lm(self, x, iteration_limit, damping, max_step, tolerance=0.0, n_points=1.0, prior_weight=None,
+                   device_loop=None):
         """The LevenbergMarquardt loop over value_gradient_hessian in one native
         call (fsdf_descend_lm); rigid scenes. Returns (x, f, evaluations, final
-        damping)."""
+        damping). Both options hold for this call alone; the context is as it
+        was on return. prior_weight (a scalar or one value per coordinate): the
+        prior Σ μ_i (x_i − x_i at entry)² on the wrapped objective
+        (fsdf_set_lm_prior; set after the mechanism is registered, cleared
+        again). device_loop (False / True / "require"): the LM loop
+        (fsdf_set_lm_solver); None: the context's own mode
+        (Context.set_lm_solver)."""
         self._native_rigid("descend_lm")
-        return self.ctx.descend_lm(x, iteration_limit, damping, max_step, tolerance, n_points)
+        ctx = self.ctx
+        mode = getattr(ctx, "lm_solver_mode", 0)
+        try:
+            if device_loop is not None:
+                ctx.set_lm_solver(device_loop)
+            if prior_weight is not None:
+                ctx.set_lm_prior(prior_weight)
+            return ctx.descend_lm(x, iteration_limit, damping, max_step, tolerance, n_points)
+        finally:
+            if prior_weight is not None:
+                ctx.set_lm_prior(None)
+            if device_loop is not None:
+                ctx.set_lm_solver(mode)
 
     def per_point(self, x):
         """(d*, k*, ∇d*) for every sensed point at configuration x."""

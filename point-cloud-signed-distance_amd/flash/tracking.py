@@ -71,6 +71,40 @@ class NaiveSolver:
         return x, f
 
 
+def state_prior(value_gradient_hessian, x_ref, weight):
+    """Wrap an objective x -> (f, g, H) in a prior on the frame's start state:
+    F(x) = f(x) + Σ_i μ_i (x_i − x̄_i)², x̄ = x_ref, μ = weight (a scalar or one
+    value per coordinate, each >= 0). Gauss-Newton moves the coordinates a noisy
+    cloud does not determine (IRB140's wrist: H_ii/N of 6e-5 .. 3e-9 against
+    1e-2 .. 7e-2 for joints 1-3) by 1-1.5 rad for a last 1e-6 of cost; μ = 1e-3
+    keeps them within ~0.1 rad of x̄ (tests/test_lm_prior.py). The arithmetic is
+    fsdf_set_lm_prior's, operation for operation (the same bits as
+    fsdf_descend_lm with that prior): e = x − x̄; r = 0.0, r += μ_i (e_i e_i) in
+    index order; f + r; g_i + (2 μ_i) e_i; H_ii + 2 μ_i. Quaternion coordinates
+    are penalised raw: a weight there also fixes the quaternion's scale.
+    weight None: the objective itself, untouched."""
+    if weight is None:
+        return value_gradient_hessian
+    x_ref = np.array(x_ref, np.float64, copy=True).reshape(-1)
+    mu = np.broadcast_to(np.asarray(weight, np.float64), x_ref.shape).copy()
+    if not (np.all(np.isfinite(mu)) and np.all(mu >= 0.0)):
+        raise ValueError("state_prior: weights must be finite and >= 0")
+    two_mu = 2.0 * mu
+
+    def wrapped(x):
+        f, g, H = value_gradient_hessian(x)
+        e = np.asarray(x, np.float64).reshape(-1) - x_ref
+        r = 0.0
+        for m, v in zip(mu, e):  # (summed in index order: the native loop's bits)
+            r += float(m) * (float(v) * float(v))
+        H = np.array(H, np.float64, copy=True)
+        i = np.arange(x_ref.size)
+        H[i, i] = H[i, i] + two_mu
+        return float(f) + r, np.asarray(g, np.float64) + two_mu * e, H
+
+    return wrapped
+
+
 @dataclass
 class LevenbergMarquardt:
     """Damped Gauss-Newton on the sum-of-squares cost (rigid scenes): the
@@ -91,12 +125,22 @@ class LevenbergMarquardt:
     second moments are reduced on the device (fsdf_value_gradient_hessian), and
     without a callback the whole loop runs natively (fsdf_descend_lm, the same
     bits). Scenes with RBF skins or deformations have no Gauss-Newton matrix
-    here: NotImplementedError."""
+    here: NotImplementedError.
+    prior_weight (a scalar or one value per coordinate; None: no prior): in
+    estimate_state / Tracker / track the objective gains state_prior's Σ μ_i
+    (x_i − x̄_i)² about the frame's warm start x̄ — through the context on the
+    native path (fsdf_set_lm_prior), through state_prior with a callback;
+    `optimize` itself takes the objective as given (wrap it in state_prior).
+    device_loop (False, True or "require"): the native path's loop
+    (fsdf_set_lm_solver): False the host loop, True the device-resident loop
+    where the scene fits, "require" an error otherwise; the same bits."""
     num_vars: int
     damping: float = 1e-3
     max_step: float = 0.5
     iteration_limit: int = 30
     gradient_convergence_tolerance: float = 1e-6
+    prior_weight: float | np.ndarray | None = None
+    device_loop: bool | str = False
     iterations: int = field(default=0, init=False)  # evaluations of the last optimize
     final_damping: float = field(default=0.0, init=False)
 
@@ -145,7 +189,9 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
     """wrapped_cost (src/tracking.jl:16-21) over a CostFunctor, then optimize!.
     Without a callback, a NaiveSolver runs natively (fsdf_descend: the same
     arithmetic, no Python round trip per iteration), and so does a
-    LevenbergMarquardt on a native rigid scene (fsdf_descend_lm)."""
+    LevenbergMarquardt on a native rigid scene (fsdf_descend_lm, with the
+    solver's prior_weight and device_loop); with a callback its Python loop
+    runs over the objective wrapped in state_prior."""
     n = max(n_points, 1)
     if callback is None and type(solver) is NaiveSolver and cost._native:
         x0 = np.asarray(x_estimated, np.float64)
@@ -166,7 +212,8 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
         x0 = np.asarray(x_estimated, np.float64)
         if callback is None and type(solver) is LevenbergMarquardt and hasattr(cost, "descend_lm"):
             x, _, its, lam = cost.descend_lm(x0, solver.iteration_limit, solver.damping, solver.max_step,
-                                             solver.gradient_convergence_tolerance, n)
+                                             solver.gradient_convergence_tolerance, n,
+                                             prior_weight=solver.prior_weight, device_loop=solver.device_loop)
             solver.iterations, solver.final_damping = its, lam
             return x
 
@@ -176,7 +223,7 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
                 callback(x, c)
             return c / n, g / n, H / n
 
-        x, _ = solver.optimize(wrapped_h, x0)
+        x, _ = solver.optimize(state_prior(wrapped_h, x0, solver.prior_weight), x0)
         return x
 
     def wrapped(x):

@@ -12,8 +12,13 @@ first pass and auto regroup).
 times whole estimate_state frames instead (set_points + the solver from the
 same perturbed start, as tools/descend_probe.py's): the default NaiveSolver
 (30 iterations, rate 0.1, max_step 0.5, tolerance 1e-3) against
-LevenbergMarquardt at several evaluation limits, with the f = c / n each ends
-at and the evaluations it made.
+LevenbergMarquardt at several evaluation limits (--limits), with the f = c / n
+each ends at and the evaluations it made. --device-loop runs the LM frames on
+the device-resident loop (fsdf_set_lm_solver 2) instead of the host loop;
+--prior W gives them the prior of fsdf_set_lm_prior at a uniform weight W, or
+scaled per coordinate by the points of the joint's subtree (--prior-scale
+subtree: W · N / points nearest a surface of the subtree; f is then the wrapped
+objective's, the prior included).
 
 And for the kernels' own times a kernel trace of the Hessian calls alone
 (no counters in the same run):
@@ -86,7 +91,15 @@ def frames(a):
         pts = synthetic.depth_cloud(m, q_true, n, seed=1234 + 17)
         cf = CostFunctor(m, pts)
         f_true = cf.value_and_gradient(np.asarray(q_true, np.float64))[0] / n
-        solvers = [("naive", None)] + [("lm", k) for k in (3, 4, 6, 10)]
+        solvers = [("naive", None)] + [("lm", k) for k in a.limits]
+        if a.device_loop:  # (the default is the host loop: an A/B library from before the switch runs it too)
+            cf.ctx.set_lm_solver("require")
+        prior = None
+        if a.prior is not None:
+            prior = np.full(len(q), a.prior)
+            if a.prior_scale == "subtree":
+                prior = prior * subtree_scale(m, cf, q_true, n)
+        kw = {} if prior is None else {"prior_weight": prior}
         for rep in range(2):  # (alternating: each solver's frames twice, apart)
             for name, limit in solvers:
                 ms = []
@@ -96,15 +109,36 @@ def frames(a):
                     if name == "naive":
                         x, f, its = cf.descend(q, 30, 0.1, 0.5, 1e-3, None, float(n))
                     else:
-                        x, f, its, _ = cf.descend_lm(q, limit, 1e-3, 0.5, 1e-6, float(n))
+                        x, f, its, _ = cf.descend_lm(q, limit, 1e-3, 0.5, 1e-6, float(n), **kw)
                     ms.append((time.perf_counter() - t0) * 1e3)
                 out = {"model": model, "points": n, "solver": name, "limit": limit or 30, "rep": rep,
                        "frame_ms": statistics.median(ms[1:]), "evaluations": its, "f": f, "f_at_q_true": f_true,
+                       "lm_loop": "device" if a.device_loop else "host", "prior": a.prior,
+                       "prior_scale": a.prior_scale if a.prior is not None else None,
                        "max_abs_q_error": float(np.abs(x - q_true).max())}
                 print(json.dumps(out), flush=True)
                 if a.json:
                     with open(a.json, "a") as fh:
                         fh.write(json.dumps(out) + "\n")
+
+
+def subtree_scale(m, cf, q, n):
+    """Per coordinate N / (points whose nearest surface lies in the subtree of
+    the coordinate's joint, at q): a joint that few points see gets the larger
+    weight."""
+    mech = m.mechanism
+    k = next(v for v in cf.per_point(np.asarray(q, np.float64)) if np.issubdtype(np.asarray(v).dtype, np.integer))
+    per_surface = np.bincount(k, minlength=len(m.surfaces))
+    per_body = np.zeros(mech.num_bodies)
+    for s_, c in zip(m.surfaces, per_surface):
+        per_body[s_.body] += c
+    for b in range(mech.num_bodies - 1, 0, -1):
+        per_body[mech.edges[b].parent] += per_body[b]
+    out = np.ones(mech.num_positions)
+    for b in range(1, mech.num_bodies):
+        r = mech.q_range(b)
+        out[r.start:r.stop] = n / max(per_body[b], 1.0)
+    return out
 
 
 def trace(path):
@@ -137,6 +171,10 @@ if __name__ == "__main__":
     p.add_argument("--json", default=None)
     p.add_argument("--trace", default=None)
     p.add_argument("--frames", type=int, default=0)
+    p.add_argument("--limits", type=lambda v: [int(t) for t in v.split(",")], default=[3, 4, 6, 10])
+    p.add_argument("--device-loop", action="store_true")
+    p.add_argument("--prior", type=float, default=None)
+    p.add_argument("--prior-scale", choices=["uniform", "subtree"], default="uniform")
     a = p.parse_args()
     if a.trace:
         trace(a.trace)

@@ -6,10 +6,14 @@ iterations (native FK + pose assembly, residual pass, accumulator read-back,
 chain rule). Prints ms per iteration, ms per frame, tracking error.
 
     python tools/track_bench.py [--model m64|irb140|c5] [--points N] [--frames F] [--iters I] [--solver naive|lm]
+                                [--lm-device] [--prior W]
 
 --solver lm: the frames run LevenbergMarquardt (fsdf_descend_lm; rigid models
 only) with --iters as its evaluation limit; its default tolerance ends a frame
-early. Either way the output lists each frame's evaluations and final f = c / n.
+early; --lm-device runs them on the device-resident loop (fsdf_set_lm_solver 2)
+and --prior W adds the prior of fsdf_set_lm_prior about each frame's warm start
+at a uniform weight W. Either way the output lists each frame's evaluations and
+final f = c / n.
 
 c5 = the notebook's own scene (irb_and_squishable: 7 hulls + the deformable
 squishable RBF skin + table, 63 states): the IRB's joints move between
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--solver", default="naive", choices=("naive", "lm"))
+    ap.add_argument("--lm-device", action="store_true")
+    ap.add_argument("--prior", type=float, default=None)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import flash
@@ -67,7 +73,8 @@ def main():
     if a.solver == "lm":
         if a.model == "c5":
             ap.error("--solver lm: rigid models only (m64, irb140)")
-        solver = LevenbergMarquardt(n, iteration_limit=a.iters)
+        solver = LevenbergMarquardt(n, iteration_limit=a.iters, prior_weight=a.prior,
+                                    device_loop="require" if a.lm_device else False)
     else:
         solver = NaiveSolver(n, rate=rate, max_step=0.1, iteration_limit=a.iters)
     tr = Tracker(m, state, solver)
@@ -79,6 +86,7 @@ def main():
         errs.append(float(np.abs(x[:nq] - q[:nq]).max()))
         final_f.append(tr.cost.value_and_gradient(x)[0] / len(pts))  # (outside the frame's timing)
     out = {"model": a.model, "points": a.points, "frames": a.frames - 1, "solver": a.solver,
+           "lm_device": a.lm_device, "prior": a.prior,
            "iters_per_frame": a.iters, "evaluations_per_frame": list(tr.iterations), "final_f_per_frame": final_f,
            "ms_per_iteration": tr.iteration_ms(), "ms_per_frame": float(np.mean(tr.frame_ms)),
            "set_points_ms": float(np.mean(tr.set_points_ms)),
