@@ -300,6 +300,47 @@ int fsdf_lm_minimize(fsdf_vgh_fn fn, void* user, int32_t n, double* x, int32_t i
                      double max_step, double tolerance, double* work, double* value_out, int32_t* iterations_out,
                      double* damping_out);
 
+/* ---- Gauss-Newton for RBF skins: host side (no device) --------------------------
+ * A point p whose nearest surface is an RBF skin of n centres has the residual
+ * s(p) = f/|∇f| (fsdf_set_rbf_params), and in the skin's m = 4n + 4 parameters
+ * the row j(p) ∈ R^m, laid out as the skin's accumulator block:
+ *     ∂s/∂w [n], ∂s/∂a, ∂s/∂b [3], ∂s/∂c [n][3]   (coefficients fixed for ∂s/∂c)
+ * With dsdf = 1/|∇f|, c = f/|∇f|^3, u = −c ∇f and per centre d = p − c_i,
+ * ρ = |d|, e = d·u:  ∂s/∂w_i = dsdf ρ^3 + 3 ρ e;  ∂s/∂c_i = −w_i (k1 d + 3ρ u),
+ * k1 = 3ρ dsdf + (ρ > 0 ? 3e/ρ : 0);  ∂s/∂a = dsdf;  ∂s/∂b = dsdf p + u — the
+ * summands of the accumulator block without their factor 2s (the block is
+ * Σ 2 s j). The skin's second moment is
+ *     M [m][m] = Σ_{p: k*(p) = the skin} j(p) j(p)ᵀ   (row-major, full, symmetric)
+ * (reduced on the device: fsdf_eval_skin_moments below), and ∂s/∂x = L j with L
+ * (nx x m, nx = nq + 3 n_deform) the linear map fsdf_value_and_gradient applies
+ * to the block: fsdf_rbf_adjoint, the centre forces to body wrenches and ∂/∂δ,
+ * fsdf_config_gradient. So JᵀJ gains L M Lᵀ per skin, and the Gauss-Newton
+ * Hessian of cost = Σ d*^2 + weight Σ|δ|^2 is
+ *     H = 2 (A_hulls + Σ_r L_r M_r L_rᵀ) + 2 weight I on the deformations,
+ * A_hulls = fsdf_gauss_newton_matrix over the hull surfaces, in the nq block.
+ * Replaces what the reference reaches for Ipopt for on its deformable scene
+ * (examples/squishable.ipynb). No cross terms between surfaces exist: every
+ * point has one nearest surface.
+ *
+ * fsdf_rbf_state_map: one skin's L [nx][m], row-major, built by sending the m
+ * unit blocks through that same code, so it is the gradient's map by
+ * construction, signs and quaternion projection included. Tree arrays, Rb / tb
+ * and q (the caller's, un-normalised) as fsdf_config_gradient; R [nb][9] the
+ * bodies' rotations (fsdf_tree_transforms); centres, u, lu, piv as
+ * fsdf_rbf_solve left them; body [n] each centre's body (-1: world), drow [n]
+ * its deformation row (-1: none; NULL: none has one), rows < n_deform.
+ * work = 8n + 8 + 12 nb + nx doubles. flash/rbf.py state_map is the numpy twin.
+ *
+ * fsdf_gauss_newton_add: A [nx][nx] += L M Lᵀ, symmetrised exactly: the upper
+ * triangle of A is read and added to, the lower overwritten with its mirror
+ * image. work = nx m doubles. Both: FSDF_ERR_ARG for bad arguments; limits
+ * are the caller's memory alone. */
+int fsdf_rbf_state_map(int32_t nb, const int32_t* parent, const int32_t* kind, const int32_t* qoff, const double* axis,
+                       const double* R, const double* Rb, const double* tb, const double* q, int32_t nq, int32_t n,
+                       const double* centres, const double* u, const double* lu, const int32_t* piv,
+                       const int32_t* body, const int32_t* drow, int32_t n_deform, double* work, double* L_out);
+int fsdf_gauss_newton_add(int32_t nx, int32_t m, const double* L, const double* M, double* work, double* A);
+
 /* ---- second-order solver: device side ------------------------------------------
  * The moments above, reduced on the device (csrc/moments.hip): a launch of its
  * own after the pass — the pass kernels are the headline path's, unchanged —
@@ -379,6 +420,48 @@ int fsdf_value_gradient_hessian(fsdf_ctx* ctx, const double* x, double* cost_out
 int fsdf_descend_lm(fsdf_ctx* ctx, double* x, int32_t iteration_limit, double damping, double max_step,
                     double tolerance, double n_points, double* value_out, int32_t* iterations_out,
                     double* damping_out);
+
+/* ---- Gauss-Newton for RBF skins: device side -----------------------------------
+ * The skins' second moments M_r above, reduced on the device
+ * (csrc/skin_moments.hip): a launch of its own after the pass — the pass
+ * kernels are unchanged — over the resident points, the pass's k* in resident
+ * order and the current RBF rows. Every workgroup owns one 64x64 block pair
+ * (bi <= bj) of one skin's matrix and a fixed run of 64-point chunks; it
+ * recomputes the field, forms the chunk's rows in LDS (zero for points nearest
+ * to another surface) and adds JᵀJ on the fp64 matrix unit; the finish launch
+ * sums the workgroups' partial blocks in workgroup order and mirrors the upper
+ * block pairs. No floating-point atomics: for a given cloud layout the moments
+ * are bit-identical from run to run, and exactly symmetric. All arithmetic is
+ * fp64 (fp32 contexts: their fp32 points and rows, widened). Skins of up to 124
+ * centres (n + 4 <= 128, fsdf_set_solver's own limit) are served; a larger one
+ * is FSDF_ERR_STATE. The grid and the partials' memory are functions of the
+ * point count and the skins' centre counts alone: 32 KB per workgroup, at most
+ * 1,024 workgroups' worth — 32 MB per context (beyond, a workgroup's run
+ * grows instead).
+ *
+ * fsdf_eval_skin_moments: fsdf_eval's pass over the resident cloud plus the
+ * skins' moments at the rows of the last fsdf_set_rbf_params; moments_out holds
+ * Σ_r m_r^2 doubles, the skins' [m_r][m_r] matrices one after the other in
+ * surface order (required; cost_out, accum_out may be NULL). Synchronous; needs
+ * no mechanism. Replaces forming Σ j jᵀ on the host from per-point outputs. A
+ * cloud of no points, or with no point on a skin, gives that skin exact zeros;
+ * a scene without a skin is FSDF_ERR_STATE.
+ *
+ * fsdf_set_lm_skins: enable = 0 (the default) leaves every refusal above as it
+ * is. With enable = 1 the second-order solver serves scenes with RBF skins and
+ * deformations: fsdf_value_gradient_hessian returns hess_out [nx][nx], nx =
+ * nq + 3 n_deform, the H above (the hulls' moments, the skins' moments, one
+ * fsdf_rbf_state_map and fsdf_gauss_newton_add per skin, the regulariser's
+ * 2 weight on the deformations' diagonal), cost_out and grad_out [nx]
+ * bit-identical to fsdf_value_and_gradient's; fsdf_descend_lm runs its host
+ * loop over the nx coordinates and fsdf_set_lm_prior expects n = nx;
+ * fsdf_set_lm_solver 1 takes the host loop for such scenes and 2 refuses them
+ * (FSDF_ERR_STATE: the device loop serves rigid scenes). Skins not all declared
+ * or a deformation row out of range fail as in fsdf_value_and_gradient. Rigid
+ * scenes are served as before, whatever the switch. */
+int fsdf_set_lm_skins(fsdf_ctx* ctx, int32_t enable);
+int fsdf_eval_skin_moments(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out,
+                           double* moments_out);
 
 /* ---- context ---------------------------------------------------------------- */
 int fsdf_create(fsdf_ctx** out, const fsdf_opts* opts);
@@ -553,6 +636,13 @@ int fsdf_synchronize(fsdf_ctx* ctx);
 int fsdf_profile_pass(fsdf_ctx* ctx, int32_t enable);
 int fsdf_pass_times(fsdf_ctx* ctx, double* kernel_ms_out, double* pass_ms_out, int64_t* launches_out);
 int fsdf_pass_time(fsdf_ctx* ctx, double* total_ms_out, int64_t* launches_out);
+/* The same for the skin moments (fsdf_eval_skin_moments, fsdf_value_gradient_hessian
+ * with fsdf_set_lm_skins): with profiling enabled on a scene with RBF skins, a
+ * pair of events is recorded around the skins' launches (the kernels and their
+ * finish launches; up to 256 pairs between queries). fsdf_skin_moments_time
+ * synchronizes, returns their summed time and count and resets the record
+ * (tools/skin_moments_time.py). */
+int fsdf_skin_moments_time(fsdf_ctx* ctx, double* total_ms_out, int64_t* launches_out);
 
 /* The pass-kernel variant the context's last residual pass dispatched, as
  * rocprofv3 names it without the namespace, e.g.

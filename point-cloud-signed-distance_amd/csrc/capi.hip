@@ -564,8 +564,13 @@ extern "C" int fsdf_profile_pass(fsdf_ctx* c, int32_t enable) {
     // before reading them
     for (auto& e : c->prof_ev) HIPCHECK(c, e.create(hipEventDisableSystemFence));
   }
+  if (enable && c->skin_ev.empty() && c->lm.R > 0) {
+    c->skin_ev.resize(2 * 256);
+    for (auto& e : c->skin_ev) HIPCHECK(c, e.create(hipEventDisableSystemFence));
+  }
   c->profiling = enable != 0;
   c->prof_used = 0;
+  c->skin_ev_used = 0;
   return FSDF_OK;
 }
 

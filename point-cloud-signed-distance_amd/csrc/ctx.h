@@ -156,6 +156,13 @@ struct fsdf_ctx {
   // moments.hip): the workgroups' partials, the [S][21] sums, their pinned read-back
   fsdf::DevBuf<double> moments_partials, moments;
   fsdf::PinnedBuf<double> h_moments;
+  // second moments of the RBF skins (fsdf_eval_skin_moments, fsdf_value_gradient_hessian with
+  // fsdf_set_lm_skins; skin_moments.hip): the workgroups' partial blocks, the skins' [m][m]
+  // matrices one after the other, their pinned read-back
+  fsdf::DevBuf<double> skin_partials, skin_moments;
+  fsdf::PinnedBuf<double> h_skin_moments;
+  std::vector<fsdf::Event> skin_ev;  // skin-moments timing (fsdf_profile_pass): pairs around its launches
+  size_t skin_ev_used = 0;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;
@@ -170,6 +177,7 @@ struct fsdf_ctx {
     std::vector<double> axis, AR, At, BR, Bt, frame_R, frame_t;
     std::vector<double> R, t, Rb, tb, poses, work;  // scratch
     std::vector<double> gn_work;                    // fsdf_gauss_newton_matrix's (fsdf_value_gradient_hessian)
+    std::vector<double> skin_L, skin_work, gn_hull; // fsdf_rbf_state_map's L and scratch, the hulls' [nq][nq] (lm_skins)
     // RBF surfaces (fsdf_set_rbf_centres), in surface order; n == 0: undeclared
     struct Rbf {
       int n_sp = 0, n = 0;
@@ -186,6 +194,7 @@ struct fsdf_ctx {
     std::vector<double> x_pass[2];
     int x_pass_next = 0;
   } mech;
+  int lm_skins = 0;                  // fsdf_set_lm_skins: the second-order solver serves skins and deformations
   int lm_solver_device = 0;          // fsdf_set_lm_solver: 0 host loop (default), 1 device where it fits, 2 required
   std::vector<double> lm_prior;      // fsdf_set_lm_prior: fsdf_descend_lm's prior weights (empty: none)
   // device solver loop of fsdf_descend (solver.hip): the mechanism's device
@@ -234,8 +243,11 @@ int run_pass(fsdf_ctx* c, const double* poses, const void* d_pts, int64_t n, dou
              const int* skip = nullptr);
 int ensure_outputs(fsdf_ctx* c, int64_t n);
 int ensure_host_acc(fsdf_ctx* c, int len);
-// (the pass with k*, ∇d* in resident order, then the moments: h_acc and h_moments in flight)
-int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who);
+// (the pass with k*, ∇d* in resident order, then the moments: h_acc and h_moments in flight;
+// what: kMomentsRigid the hulls' of a rigid scene, kMomentsAll the hulls' and the skins'
+// (h_skin_moments) of any scene, kMomentsSkins the skins' alone)
+enum { kMomentsRigid = 0, kMomentsAll = 1, kMomentsSkins = 2 };
+int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who, int what = kMomentsRigid);
 int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
           double* grad_out, bool want_pp);
 #pragma GCC visibility pop

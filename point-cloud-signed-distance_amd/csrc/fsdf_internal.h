@@ -63,6 +63,9 @@
 #ifndef FSDF_ORDER_EVERY
 #define FSDF_ORDER_EVERY 16  // passes between rebuilds of the block order / the plan
 #endif
+#ifndef FSDF_SKIN_MOMENTS_FMA
+#define FSDF_SKIN_MOMENTS_FMA 0  // skin_moments.hip: JᵀJ by v_fma_f64 inner products instead of the fp64 MFMA (A/B)
+#endif
 #ifndef FSDF_MAX_BLOCKS
 #define FSDF_MAX_BLOCKS 16384  // pass grid cap (grid-stride beyond)
 #endif
@@ -262,6 +265,45 @@ size_t moments_partials_len(int64_t n, int S);
 // evaluations a finished device LM frame still has queued, solver.hip)
 hipError_t launch_moments(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_grad, int64_t n,
                           int S, double* d_partials, double* d_moments, hipStream_t s, const int* skip = nullptr);
+
+// ---- second moments of RBF skins (skin_moments.hip) ----------------------------
+// Per skin r of n centres, m = 4n + 4: M_r [m][m] = Σ_{p: k*(p) = r's surface}
+// j(p) j(p)ᵀ, j the point's row in the layout of the skin's accumulator block
+// (include/flashsdf.h "Gauss-Newton for RBF skins"), full, row-major, exactly
+// symmetric; the skins' matrices one after the other in surface order. From
+// the resident points, the pass's k* in RESIDENT order and the context's
+// current RBF rows; all arithmetic fp64 (fp32 points and rows are widened).
+// A unit is one 64x64 block pair (bi <= bj) of one skin; workgroup
+// (unit, g) sums the chunks [g · run, (g + 1) · run) into its block on the
+// fp64 matrix unit and writes it as one partial of 4096 doubles (32 KB); the
+// finish launch sums a unit's partials in workgroup order and mirrors the
+// block. run = skin_moments_run(n, U): at least kSkinMinChunks, and as many
+// as keep U · groups <= kSkinMaxPartials — the partials take at most
+// kSkinMaxPartials · 32 KB = 32 MB per context, a function of (n, the skins'
+// centre counts) alone, as the grid is.
+constexpr int kSkinMaxCentres = 124;     // n + 4 <= 128, the device solver's own limit
+constexpr int kSkinMaxUnits = 64;        // Σ (4n + 4) <= kMaxRbfAccum: at most 64 skins, at most 64 block pairs
+constexpr int kSkinBlock = 256;          // 4 waves: a 16x64 strip of the block each
+constexpr int kSkinTile = 64;            // side of a unit's output block
+constexpr int kSkinMinChunks = 8;        // a workgroup's run of 64-point chunks, at least (a multiple of 4)
+constexpr int kSkinMaxPartials = 1024;   // partial blocks, at most (one workgroup's run is the whole cloud beyond)
+struct SkinPlan {                        // (host side: a pair of launches per skin)
+  int U = 0, R = 0;                      // units, skins
+  int unit0[kSkinMaxUnits];              // skin r's units are [unit0[r], unit0[r + 1]): its pairs, bi-major
+  int n[kSkinMaxUnits], row_off[kSkinMaxUnits], surf[kSkinMaxUnits], mom_off[kSkinMaxUnits];
+  int total = 0;                         // Σ m_r²
+};
+// the plan of a surface list (kind [S], centres [S]); false: a skin of more
+// than kSkinMaxCentres centres (or no skin at all)
+bool skin_moments_plan(int S, const int32_t* kind, const int32_t* n_centers, SkinPlan* out);
+int64_t skin_moments_run(int64_t n, int U);
+int skin_moments_groups(int64_t n, int U);
+size_t skin_moments_partials_len(int64_t n, int U);  // doubles of d_partials
+// n > 0. d_rows: the RBF rows of the context precision (PosedModel::rbf_rows);
+// d_moments [plan.total]. skip as launch_moments'.
+hipError_t launch_skin_moments(int precision, const void* d_pts, const int32_t* d_kstar, const void* d_rows, int64_t n,
+                               const SkinPlan& plan, double* d_partials, double* d_moments, hipStream_t s,
+                               const int* skip = nullptr);
 
 hipError_t launch_to_f32(const double* src, float* dst, int64_t count, hipStream_t s);
 

@@ -1,7 +1,8 @@
 // gauss_newton.cpp — host side of the second-order tracking solver (no device):
 // the Gauss-Newton matrix of the mechanism from the per-surface second moments
 // of the residual, one damped (Levenberg-Marquardt) step, and the loop over it
-// (fsdf_lm_minimize).
+// (fsdf_lm_minimize); for RBF skins the term L M Lᵀ of one skin
+// (fsdf_gauss_newton_add).
 //
 // For a point p on a surface of body b, ∂d*(p)/∂x_i = s_i · w_p, with w_p =
 // (∇d*, p × ∇d*) and s_i the motion row of joint coordinate i — the row the
@@ -83,6 +84,30 @@ extern "C" int fsdf_gauss_newton_matrix(int32_t nb, const int32_t* parent, const
       }
     }
   }
+  return FSDF_OK;
+}
+
+// A += L M Lᵀ for one RBF skin (L from fsdf_rbf_state_map, M its second
+// moment, skin_moments.hip): T = L M, then the upper triangle of T Lᵀ is added
+// to A's and mirrored, so A is exactly symmetric whatever rounding M carries.
+extern "C" int fsdf_gauss_newton_add(int32_t nx, int32_t m, const double* L, const double* M, double* work,
+                                     double* A) {
+  if (nx < 0 || m < 0 || ((nx > 0 && m > 0) && (!L || !M || !work)) || (nx > 0 && !A)) return FSDF_ERR_ARG;
+  double* T = work;  // [nx][m]
+  for (int i = 0; i < nx; ++i)
+    for (int k = 0; k < m; ++k) {
+      double s = 0.0;
+      for (int l = 0; l < m; ++l) s += L[(size_t)i * m + l] * M[(size_t)l * m + k];
+      T[(size_t)i * m + k] = s;
+    }
+  for (int i = 0; i < nx; ++i)
+    for (int j = i; j < nx; ++j) {
+      double s = 0.0;
+      for (int k = 0; k < m; ++k) s += T[(size_t)i * m + k] * L[(size_t)j * m + k];
+      const double a = A[(size_t)i * nx + j] + s;
+      A[(size_t)i * nx + j] = a;
+      A[(size_t)j * nx + i] = a;
+    }
   return FSDF_OK;
 }
 

@@ -1,7 +1,8 @@
 // iterate.hip — iterations of a registered mechanism: fsdf_set_mechanism, RBF
 // centres and deformations, the host halves of one CostFunctor iteration
 // (FK, weight solve, chain rule) around a pass, the same with the Gauss-Newton
-// Hessian (fsdf_value_gradient_hessian) and its Levenberg-Marquardt loop
+// Hessian (fsdf_value_gradient_hessian; with fsdf_set_lm_skins also for scenes
+// with RBF skins and deformations) and its Levenberg-Marquardt loop
 // (fsdf_descend_lm, with the prior of fsdf_set_lm_prior, on the host or —
 // fsdf_set_lm_solver — on the device), and the solver loops of fsdf_descend on
 // the host and on the device (solver.hip).
@@ -301,7 +302,7 @@ extern "C" int fsdf_value_and_gradient(fsdf_ctx* c, const double* x, double* cos
 }
 
 // fsdf_value_and_gradient with the Gauss-Newton Hessian 2 JᵀJ of the same pass
-// (rigid scenes): the pass also writes k* and ∇d* in resident order, the
+// (rigid scenes; others below, behind fsdf_set_lm_skins): the pass also writes k* and ∇d* in resident order, the
 // moments launch (moments.hip) reduces them per surface, and
 // fsdf_gauss_newton_matrix contracts them with that pass's FK. The auto
 // regroup is queued after the moments launch: they read the layout the pass
@@ -311,14 +312,15 @@ extern "C" int fsdf_value_gradient_hessian(fsdf_ctx* c, const double* x, double*
   if (!c) return FSDF_ERR_ARG;
   if (!x || !cost_out || !grad_out || !hess_out)
     return fail(c, FSDF_ERR_ARG, "value_gradient_hessian: null argument");
-  if (c->lm.R > 0 || c->mech.n_deform > 0)
+  const bool rigid = c->lm.R == 0 && c->mech.n_deform == 0;
+  if (!rigid && !c->lm_skins)
     return fail(c, FSDF_ERR_STATE,
                 "value_gradient_hessian: the Gauss-Newton matrix is defined for rigid scenes (no RBF skin, no "
                 "deformation)");
   int rc = iteration_prepare(c, x, "value_gradient_hessian");
   if (rc) return rc;
   auto& M = c->mech;
-  rc = run_pass_moments(c, M.poses.data(), "value_gradient_hessian");
+  rc = run_pass_moments(c, M.poses.data(), "value_gradient_hessian", rigid ? kMomentsRigid : kMomentsAll);
   if (rc) return rc;
   rc = iteration_regroup(c);  // (stream-ordered after the pass and the moments: the sync below covers it)
   if (rc) return rc;
@@ -327,11 +329,44 @@ extern "C" int fsdf_value_gradient_hessian(fsdf_ctx* c, const double* x, double*
   if (rc) return rc;
   const int nq = M.nq;
   M.gn_work.resize((size_t)36 * M.nb + (size_t)6 * nq);
+  if (rigid) {
+    rc = fsdf_gauss_newton_matrix(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.Rb.data(),
+                                  M.tb.data(), x, c->lm.S, M.surface_body.data(), c->h_moments.get(), nq,
+                                  M.gn_work.data(), hess_out);
+    if (rc) return fail(c, rc, "value_gradient_hessian: Gauss-Newton matrix");
+    for (size_t i = 0; i < (size_t)nq * nq; ++i) hess_out[i] = 2.0 * hess_out[i];
+    return FSDF_OK;
+  }
+  // skins and deformations (fsdf_set_lm_skins): A = A_hulls in the nq block +
+  // Σ_r L_r M_r L_rᵀ over the nx = nq + 3 n_deform coordinates, H = 2 A +
+  // 2 weight I on the deformations (the regulariser is a sum of squares too)
+  const int nx = nq + 3 * M.n_deform, S = c->lm.S;
+  double* hm = c->h_moments.get();
+  for (int k = 0; k < S; ++k)  // (a skin's points have no hull moments)
+    if (c->h_surface_kind[k] != FSDF_SURFACE_HULL)
+      for (int e = 0; e < fsdf::kMomentsLen; ++e) hm[(size_t)fsdf::kMomentsLen * k + e] = 0.0;
+  M.gn_hull.resize((size_t)nq * nq);
   rc = fsdf_gauss_newton_matrix(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.Rb.data(),
-                                M.tb.data(), x, c->lm.S, M.surface_body.data(), c->h_moments.get(), nq,
-                                M.gn_work.data(), hess_out);
+                                M.tb.data(), x, S, M.surface_body.data(), hm, nq, M.gn_work.data(), M.gn_hull.data());
   if (rc) return fail(c, rc, "value_gradient_hessian: Gauss-Newton matrix");
-  for (size_t i = 0; i < (size_t)nq * nq; ++i) hess_out[i] = 2.0 * hess_out[i];
+  for (size_t i = 0; i < (size_t)nx * nx; ++i) hess_out[i] = 0.0;
+  for (int i = 0; i < nq; ++i)
+    for (int j = 0; j < nq; ++j) hess_out[(size_t)i * nx + j] = M.gn_hull[(size_t)i * nq + j];
+  const double* sm = c->h_skin_moments.get();
+  for (auto& D : M.rbf) {
+    const int m = 4 * D.n + 4;
+    M.skin_L.resize((size_t)nx * m);
+    M.skin_work.resize(std::max((size_t)8 * D.n + 8 + (size_t)12 * M.nb + nx, (size_t)nx * m));
+    rc = fsdf_rbf_state_map(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.R.data(),
+                            M.Rb.data(), M.tb.data(), x, nq, D.n, D.centres.data(), D.u.data(), D.lu.data(),
+                            D.piv.data(), D.body.data(), D.drow.data(), M.n_deform, M.skin_work.data(),
+                            M.skin_L.data());
+    if (!rc) rc = fsdf_gauss_newton_add(nx, m, M.skin_L.data(), sm, M.skin_work.data(), hess_out);
+    if (rc) return fail(c, rc, "value_gradient_hessian: the skins' Gauss-Newton term");
+    sm += (size_t)m * m;
+  }
+  for (size_t i = 0; i < (size_t)nx * nx; ++i) hess_out[i] = 2.0 * hess_out[i];
+  for (int i = nq; i < nx; ++i) hess_out[(size_t)i * nx + i] += 2.0 * M.weight;
   return FSDF_OK;
 }
 
@@ -394,6 +429,13 @@ extern "C" int fsdf_set_lm_solver(fsdf_ctx* c, int32_t device_loop) {
   if (!c) return FSDF_ERR_ARG;
   if (device_loop < 0 || device_loop > 2) return fail(c, FSDF_ERR_ARG, "set_lm_solver: mode %d", device_loop);
   c->lm_solver_device = device_loop;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_lm_skins(fsdf_ctx* c, int32_t enable) {
+  if (!c) return FSDF_ERR_ARG;
+  if (enable != 0 && enable != 1) return fail(c, FSDF_ERR_ARG, "set_lm_skins: enable %d", enable);
+  c->lm_skins = enable;
   return FSDF_OK;
 }
 
@@ -520,21 +562,26 @@ extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, 
   if (!x || iteration_limit < 0 || !(n_points > 0.0) || !std::isfinite(damping) || !(max_step >= 0.0))
     return fail(c, FSDF_ERR_ARG, "descend_lm: bad arguments");
   if (c->mech.nb == 0) return fail(c, FSDF_ERR_STATE, "descend_lm: no mechanism (call fsdf_set_mechanism)");
-  if (c->lm.R > 0 || c->mech.n_deform > 0)
+  const bool rigid = c->lm.R == 0 && c->mech.n_deform == 0;
+  if (!rigid && !c->lm_skins)
     return fail(c, FSDF_ERR_STATE, "descend_lm: rigid scenes only (no RBF skin, no deformation)");
   const auto& Mc = c->mech;
   if ((int)Mc.surface_body.size() != c->lm.S || (int)Mc.poses.size() != 12 * c->lm.S)
     return fail(c, FSDF_ERR_STATE,
                 "descend_lm: mechanism registered for another surface list (call fsdf_set_mechanism)");
-  const int nq = c->mech.nq;
+  // (the state: the joint coordinates, then — fsdf_set_lm_skins — the deformations)
+  const int nq = c->mech.nq + 3 * c->mech.n_deform;
   const bool prior = !c->lm_prior.empty();
   if (prior && (int)c->lm_prior.size() != nq)
     return fail(c, FSDF_ERR_STATE, "descend_lm: the prior has %d weights, the mechanism %d coordinates",
                 (int)c->lm_prior.size(), nq);
+  if (!rigid && c->lm_solver_device == 2)
+    return fail(c, FSDF_ERR_STATE, "descend_lm: the device loop was required (fsdf_set_lm_solver 2) but the scene "
+                                   "has RBF skins / deformations (their loop runs on the host)");
   // the device loop (fsdf_set_lm_solver 1 / 2): a finite damping > 0 (the
   // step's raises of a degenerate factorisation are then bounded), resident
   // points, the moments table and both solver kernels' carves within their LDS
-  if (c->lm_solver_device && iteration_limit > 0) {
+  if (rigid && c->lm_solver_device && iteration_limit > 0) {
     const bool required = c->lm_solver_device == 2;
     if (required && !(damping > 0.0))
       return fail(c, FSDF_ERR_ARG, "descend_lm: the device loop needs a damping > 0");

@@ -348,24 +348,41 @@ extern "C" int fsdf_eval(fsdf_ctx* c, const double* poses, double* cost_out, dou
 // only then are their pointers read with get(), into locals; (3) the launches
 // take those locals. No context buffer is named as an argument of a call that
 // may reserve. A cloud of no points launches no moments kernel: zero moments.
-int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who) {
+// what (ctx.h): kMomentsRigid is the above and refuses other scenes;
+// kMomentsAll serves any scene (fsdf_set_lm_skins) and adds the RBF skins' own
+// second moments (skin_moments.hip) into c->h_skin_moments, from the same k*
+// and the rows the pass read; kMomentsSkins leaves the hulls' out
+// (fsdf_eval_skin_moments).
+int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who, int what) {
   const int S = c->lm.S;
-  if (c->lm.R > 0 || c->mech.n_deform > 0)
+  if (what == kMomentsRigid && (c->lm.R > 0 || c->mech.n_deform > 0))
     return fail(c, FSDF_ERR_STATE, "%s: the second moments are defined for rigid scenes (no RBF skin, no deformation)",
                 who);
-  if (!fsdf::moments_fit(S))
+  const bool hulls = what != kMomentsSkins, skins = what != kMomentsRigid && c->lm.R > 0;
+  if (hulls && !fsdf::moments_fit(S))
     return fail(c, FSDF_ERR_STATE, "%s: the moments table of %d surfaces (%zu bytes) does not fit %d bytes of LDS", who,
                 S, (size_t)S * fsdf::kMomentsLen * sizeof(double), fsdf::kMomentsMaxLds);
+  fsdf::SkinPlan plan;
+  if (skins && !fsdf::skin_moments_plan(S, c->h_surface_kind.data(), c->h_n_centers.data(), &plan))
+    return fail(c, FSDF_ERR_STATE, "%s: the skin moments serve skins of at most %d centres (n + 4 <= 128)", who,
+                fsdf::kSkinMaxCentres);
   const int64_t n = c->n;
-  const size_t mlen = (size_t)S * fsdf::kMomentsLen;
+  const size_t mlen = (size_t)S * fsdf::kMomentsLen, slen = skins ? (size_t)plan.total : 0;
   // (1) reserve
   int rc = ensure_outputs(c, n);
   if (rc) return rc;
   rc = ensure_host_acc(c, accum_len(c));
   if (rc) return rc;
-  HIPCHECK(c, c->moments_partials.reserve(fsdf::moments_partials_len(n, S)));
-  HIPCHECK(c, c->moments.reserve(mlen));
-  HIPCHECK(c, c->h_moments.reserve(mlen));
+  if (hulls) {
+    HIPCHECK(c, c->moments_partials.reserve(fsdf::moments_partials_len(n, S)));
+    HIPCHECK(c, c->moments.reserve(mlen));
+    HIPCHECK(c, c->h_moments.reserve(mlen));
+  }
+  if (skins) {
+    HIPCHECK(c, c->skin_partials.reserve(fsdf::skin_moments_partials_len(n, plan.U)));
+    HIPCHECK(c, c->skin_moments.reserve(slen));
+    HIPCHECK(c, c->h_skin_moments.reserve(slen));
+  }
   // (2) read the pointers
   const void* d_pts = c->cur.pts.get();
   int32_t* d_kstar = c->kstar.get();
@@ -373,17 +390,36 @@ int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who) {
   double* d_partials = c->moments_partials.get();
   double* d_moments = c->moments.get();
   double* h_moments = c->h_moments.get();
+  double* d_skin_partials = c->skin_partials.get();
+  double* d_skin_moments = c->skin_moments.get();
+  double* h_skin_moments = c->h_skin_moments.get();
   double* d_acc_host = nullptr;
   HIPCHECK(c, hipHostGetDevicePointer((void**)&d_acc_host, c->h_acc.get(), 0));
   // (3) launch: the pass with k* and ∇d* in resident order (no permutation), the moments, their read-back
   rc = run_pass(c, poses, d_pts, n, d_acc_host, d_kstar, nullptr, d_grad, nullptr, true);
   if (rc) return rc;
   if (n == 0) {
-    memset(h_moments, 0, mlen * sizeof(double));
+    if (hulls) memset(h_moments, 0, mlen * sizeof(double));
+    if (skins) memset(h_skin_moments, 0, slen * sizeof(double));
     return FSDF_OK;
   }
-  HIPCHECK(c, fsdf::launch_moments(c->precision, d_pts, d_kstar, d_grad, n, S, d_partials, d_moments, c->stream));
-  HIPCHECK(c, hipMemcpyAsync(h_moments, d_moments, mlen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (hulls) {
+    HIPCHECK(c, fsdf::launch_moments(c->precision, d_pts, d_kstar, d_grad, n, S, d_partials, d_moments, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(h_moments, d_moments, mlen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (skins) {  // (the rows the pass just read: fsdf_set_rbf_params' last, in order on the stream)
+    // (profiling: a pair of events around the skins' launches, fsdf_skin_moments_time)
+    const bool prof = c->profiling && c->skin_ev_used + 2 <= c->skin_ev.size();
+    if (prof) HIPCHECK(c, hipEventRecord(c->skin_ev[c->skin_ev_used], c->stream));
+    HIPCHECK(c, fsdf::launch_skin_moments(c->precision, d_pts, d_kstar, c->pm.rbf_rows, n, plan, d_skin_partials,
+                                          d_skin_moments, c->stream));
+    if (prof) {
+      HIPCHECK(c, hipEventRecord(c->skin_ev[c->skin_ev_used + 1], c->stream));
+      c->skin_ev_used += 2;
+    }
+    HIPCHECK(c, hipMemcpyAsync(h_skin_moments, d_skin_moments, slen * sizeof(double), hipMemcpyDeviceToHost,
+                               c->stream));
+  }
   return FSDF_OK;
 }
 
@@ -400,5 +436,43 @@ extern "C" int fsdf_eval_moments(fsdf_ctx* c, const double* poses, double* cost_
   if (cost_out) *cost_out = acc[0];
   if (accum_out) memcpy(accum_out, acc, (size_t)accum_len(c) * sizeof(double));
   memcpy(moments_out, c->h_moments.get(), (size_t)c->lm.S * fsdf::kMomentsLen * sizeof(double));
+  return FSDF_OK;
+}
+
+// fsdf_eval's pass and the second moments of the scene's RBF skins
+// (skin_moments.hip), at the rows of the last fsdf_set_rbf_params.
+extern "C" int fsdf_eval_skin_moments(fsdf_ctx* c, const double* poses, double* cost_out, double* accum_out,
+                                      double* moments_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval_skin_moments: no model (call fsdf_set_surfaces first)");
+  if (!poses || !moments_out) return fail(c, FSDF_ERR_ARG, "eval_skin_moments: poses and moments_out are required");
+  if (c->lm.R == 0) return fail(c, FSDF_ERR_STATE, "eval_skin_moments: the scene has no RBF skin");
+  HIPCHECK(c, hipSetDevice(c->device));
+  const int rc = run_pass_moments(c, poses, "eval_skin_moments", kMomentsSkins);
+  if (rc) return rc;
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  const double* acc = c->h_acc.get();
+  if (cost_out) *cost_out = acc[0];
+  if (accum_out) memcpy(accum_out, acc, (size_t)accum_len(c) * sizeof(double));
+  size_t total = 0;
+  for (int k = 0; k < c->lm.S; ++k)
+    if (c->h_n_centers[k] > 0) total += (size_t)(4 * c->h_n_centers[k] + 4) * (size_t)(4 * c->h_n_centers[k] + 4);
+  memcpy(moments_out, c->h_skin_moments.get(), total * sizeof(double));
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_skin_moments_time(fsdf_ctx* c, double* total_ms, int64_t* launches) {
+  if (!c || !total_ms || !launches) return FSDF_ERR_ARG;
+  HIPCHECK(c, hipSetDevice(c->device));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  double t = 0.0;
+  for (size_t i = 0; i + 1 < c->skin_ev_used; i += 2) {
+    float ms = 0.f;
+    HIPCHECK(c, hipEventElapsedTime(&ms, c->skin_ev[i], c->skin_ev[i + 1]));
+    t += ms;
+  }
+  *total_ms = t;
+  *launches = (int64_t)(c->skin_ev_used / 2);
+  c->skin_ev_used = 0;
   return FSDF_OK;
 }

@@ -1,6 +1,7 @@
 // rbf_sdf.h — RBF interpolating skins in the pass kernels: the field, the
 // skin's signed distance, the adjoint sums of the lanes nearest to a skin.
-// Only sdf_kernels.hip includes it (through scene_eval.h).
+// sdf_kernels.hip includes it (through scene_eval.h), and skin_moments.hip
+// for the field's types and rbf_skin_from_field.
 #pragma once
 #include "sdf_device_math.h"
 

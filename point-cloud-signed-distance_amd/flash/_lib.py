@@ -115,6 +115,12 @@ _PROTOS = {
                                   POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
     "fsdf_set_lm_prior": (c_int32, [c_void_p, c_void_p, c_int32]),
     "fsdf_set_lm_solver": (c_int32, [c_void_p, c_int32]),
+    "fsdf_rbf_state_map": (c_int32, [c_int32] + [c_void_p] * 8 + [c_int32, c_int32] + [c_void_p] * 6 + [c_int32] +
+                           [c_void_p] * 2),
+    "fsdf_gauss_newton_add": (c_int32, [c_int32, c_int32] + [c_void_p] * 4),
+    "fsdf_set_lm_skins": (c_int32, [c_void_p, c_int32]),
+    "fsdf_skin_moments_time": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
+    "fsdf_eval_skin_moments": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -439,6 +445,21 @@ class Context:
               "eval_moments")
         return cost.value, accum, mom
 
+    def eval_skin_moments(self, poses):
+        """fsdf_eval_skin_moments: one pass over the resident cloud and the
+        second moments of its RBF skins at the current rows (set_rbf_params),
+        reduced on the device -> (cost, accum, [M_r [4n+4, 4n+4] per skin, in
+        surface order])."""
+        p = self._poses(poses)
+        accum = np.empty(self.accum_len, np.float64)
+        ms = [4 * n + 4 for n in self.rbf_centres]
+        flat = np.empty(sum(m * m for m in ms), np.float64)
+        cost = c_double(0.0)
+        check(self._lib.fsdf_eval_skin_moments(self._ctx, ptr(p), ctypes.byref(cost), ptr(accum), ptr(flat)),
+              self._ctx, "eval_skin_moments")
+        off = np.concatenate([[0], np.cumsum([m * m for m in ms])]).astype(int)
+        return cost.value, accum, [flat[off[i]: off[i + 1]].reshape(m, m) for i, m in enumerate(ms)]
+
     def eval_device(self, poses, d_accum: int, d_kstar: int = 0, d_d: int = 0, d_grad: int = 0):
         """Asynchronous pass writing into device buffers (raw device pointers)."""
         p = self._poses(poses)
@@ -491,6 +512,14 @@ class Context:
         """(summed whole-pass milliseconds, launches) since the last query."""
         ms, n = c_double(0.0), c_int64(0)
         check(self._lib.fsdf_pass_time(self._ctx, ctypes.byref(ms), ctypes.byref(n)), self._ctx, "pass_time")
+        return ms.value, n.value
+
+    def skin_moments_time(self):
+        """(summed milliseconds of the skin-moments launches, their count)
+        since the last query (profile_pass on)."""
+        ms, n = c_double(0.0), c_int64(0)
+        check(self._lib.fsdf_skin_moments_time(self._ctx, ctypes.byref(ms), ctypes.byref(n)), self._ctx,
+              "skin_moments_time")
         return ms.value, n.value
 
     def pass_times(self):
@@ -588,9 +617,10 @@ class Context:
 
     def value_gradient_hessian(self, x):
         """(cost, ∂cost/∂x, the Gauss-Newton Hessian 2 JᵀJ) in one native call
-        (fsdf_value_gradient_hessian; rigid scenes)."""
+        (fsdf_value_gradient_hessian; rigid scenes, and with set_lm_skins(True)
+        scenes with RBF skins and deformations: x, g and H over nq + 3 n_deform)."""
         x = self._state_vector(x, "value_gradient_hessian")
-        g = np.empty(x.size)  # (nq: a scene with deformations is refused)
+        g = np.empty(x.size)
         H = np.empty((x.size, x.size))
         c = c_double(0.0)
         check(self._lib.fsdf_value_gradient_hessian(self._ctx, ptr(x), ctypes.byref(c), ptr(g), ptr(H)), self._ctx,
@@ -620,9 +650,16 @@ class Context:
             if not hasattr(self, "nq"):
                 raise ValueError("set_lm_prior: a scalar weight needs the mechanism's coordinate count "
                                  "(call set_mechanism first)")
-            w = np.full(self.nq, float(w))
+            n = self.nq + (3 * getattr(self, "n_deform", 0) if getattr(self, "lm_skins", False) else 0)
+            w = np.full(n, float(w))
         w = np.ascontiguousarray(w).reshape(-1)
         check(self._lib.fsdf_set_lm_prior(self._ctx, ptr(w), w.size), self._ctx, "set_lm_prior")
+
+    def set_lm_skins(self, enable: bool):
+        """fsdf_set_lm_skins: value_gradient_hessian and descend_lm serve scenes
+        with RBF skins and deformations (off by default: they are refused)."""
+        check(self._lib.fsdf_set_lm_skins(self._ctx, int(bool(enable))), self._ctx, "set_lm_skins")
+        self.lm_skins = bool(enable)
 
     def set_lm_solver(self, device_loop):
         """fsdf_set_lm_solver: descend_lm's loop on the host (False / 0, the

@@ -113,7 +113,7 @@ class CostFunctor:
     every evaluation); each call ships only the hull poses."""
 
     def __init__(self, manipulator: Manipulator, sensed_points, device: int = 0, precision: int = 64,
-                 deformation_cost_weight=default_deformation_cost_weight):
+                 deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False):
         self.manipulator = manipulator
         self.sensed_points = np.ascontiguousarray(sensed_points, np.float64).reshape(-1, 3)
         self.weight = deformation_cost_weight
@@ -132,6 +132,21 @@ class CostFunctor:
             manipulator.num_deformations() == 0
         if self._native and getattr(self.ctx, "_mechanism_of", None) != (manipulator, self.weight):
             self._register_native()
+        # skin_hessian: value_gradient_hessian / descend_lm also serve RBF skins
+        # and deformations (fsdf_set_lm_skins; the skins' second moments are
+        # reduced on the device, csrc/skin_moments.hip)
+        self.skin_hessian = False
+        if skin_hessian:
+            self.set_skin_hessian(True)
+
+    def set_skin_hessian(self, enable: bool = True):
+        """Turn the Gauss-Newton Hessian of non-rigid scenes on or off
+        (fsdf_set_lm_skins); native scenes only."""
+        if enable and not self._native:
+            raise NotImplementedError("skin_hessian: scene is not native-capable")
+        self.skin_hessian = bool(enable)
+        if self._native:
+            self.ctx.set_lm_skins(self.skin_hessian)
 
     def _register_native(self):
         register_native(self.manipulator, self.ctx, self.weight)
@@ -205,23 +220,27 @@ class CostFunctor:
         return self.ctx.descend(x, iteration_limit, rate, max_step, tolerance, divisors, n_points)
 
     def _native_rigid(self, who):
-        if not (self._native and self.rigid):
+        if not (self._native and (self.rigid or self.skin_hessian)):
             raise NotImplementedError(f"{who}: rigid native scenes only (no RBF skin, no deformation)")
         self._ensure_resident()
         if getattr(self.ctx, "_mechanism_of", None) != (self.manipulator, self.weight):
             self._register_native()
+        if getattr(self.ctx, "lm_skins", False) != self.skin_hessian:  # (another functor of this engine set its own)
+            self.ctx.set_lm_skins(self.skin_hessian)
 
     def value_gradient_hessian(self, x):
         """(c(x), ∂c/∂x, the Gauss-Newton Hessian 2 JᵀJ) from one residual pass
         and the device reduction of its second moments
-        (fsdf_value_gradient_hessian); rigid scenes."""
+        (fsdf_value_gradient_hessian); rigid scenes, and with skin_hessian
+        scenes with RBF skins and deformations (H over the whole state)."""
         self._native_rigid("value_gradient_hessian")
         return self.ctx.value_gradient_hessian(np.asarray(x, np.float64))
 
     def descend_lm(self, x, iteration_limit, damping, max_step, tolerance=0.0, n_points=1.0, prior_weight=None,
                    device_loop=None):
         """The LevenbergMarquardt loop over value_gradient_hessian in one native
-        call (fsdf_descend_lm); rigid scenes. Returns (x, f, evaluations, final
+        call (fsdf_descend_lm); rigid scenes, and with skin_hessian scenes with
+        RBF skins and deformations (the host loop). Returns (x, f, evaluations, final
         damping). Both options hold for this call alone; the context is as it
         was on return. prior_weight (a scalar or one value per coordinate): the
         prior Σ μ_i (x_i − x_i at entry)² on the wrapped objective

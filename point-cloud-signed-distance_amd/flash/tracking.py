@@ -133,7 +133,11 @@ class LevenbergMarquardt:
     `optimize` itself takes the objective as given (wrap it in state_prior).
     device_loop (False, True or "require"): the native path's loop
     (fsdf_set_lm_solver): False the host loop, True the device-resident loop
-    where the scene fits, "require" an error otherwise; the same bits."""
+    where the scene fits, "require" an error otherwise; the same bits.
+    skins (False): True admits native scenes with RBF skins and deformations in
+    estimate_state / Tracker / track — the cost's skin_hessian is turned on
+    (fsdf_set_lm_skins: the skins' second moments reduced on the device, H over
+    the whole state [q; δ]; the host loop). The default refuses them as before."""
     num_vars: int
     damping: float = 1e-3
     max_step: float = 0.5
@@ -141,6 +145,7 @@ class LevenbergMarquardt:
     gradient_convergence_tolerance: float = 1e-6
     prior_weight: float | np.ndarray | None = None
     device_loop: bool | str = False
+    skins: bool = False
     iterations: int = field(default=0, init=False)  # evaluations of the last optimize
     final_damping: float = field(default=0.0, init=False)
 
@@ -191,7 +196,9 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
     arithmetic, no Python round trip per iteration), and so does a
     LevenbergMarquardt on a native rigid scene (fsdf_descend_lm, with the
     solver's prior_weight and device_loop); with a callback its Python loop
-    runs over the objective wrapped in state_prior."""
+    runs over the objective wrapped in state_prior. A native scene with RBF
+    skins or deformations is admitted only by LevenbergMarquardt(skins=True),
+    which turns the cost's skin_hessian on."""
     n = max(n_points, 1)
     if callback is None and type(solver) is NaiveSolver and cost._native:
         x0 = np.asarray(x_estimated, np.float64)
@@ -205,10 +212,13 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
     if isinstance(solver, LevenbergMarquardt):
         # its objective returns (f, g, H): native rigid scenes have the Hessian
         # (the second moments of the residual, reduced on the device)
-        if not (cost._native and getattr(cost, "rigid", True) and hasattr(cost, "value_gradient_hessian")):
+        skins = bool(getattr(solver, "skins", False)) and cost._native and hasattr(cost, "set_skin_hessian")
+        if not (cost._native and (getattr(cost, "rigid", True) or skins) and hasattr(cost, "value_gradient_hessian")):
             raise NotImplementedError("estimate_state: LevenbergMarquardt needs an objective with a Gauss-Newton "
                                       "Hessian: a native rigid scene (no RBF skin, no deformation); or call its "
                                       "optimize() with one")
+        if skins and not getattr(cost, "rigid", True) and not cost.skin_hessian:
+            cost.set_skin_hessian(True)
         x0 = np.asarray(x_estimated, np.float64)
         if callback is None and type(solver) is LevenbergMarquardt and hasattr(cost, "descend_lm"):
             x, _, its, lam = cost.descend_lm(x0, solver.iteration_limit, solver.damping, solver.max_step,
