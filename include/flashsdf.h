@@ -400,7 +400,7 @@ int fsdf_gauss_newton_add(int32_t nx, int32_t m, const double* L, const double* 
  * coordinates and 64 surfaces take 60 KB), FSDF_ERR_ARG for a damping that is
  * not > 0 (mode 1 then takes the host loop: the device step's raises of a
  * degenerate factorisation are bounded only from a positive damping). The
- * device loop (csrc/solver.hip) enqueues the whole frame up front, as
+ * device loop (csrc/lm_solver.hip) enqueues the whole frame up front, as
  * fsdf_descend's: FK of x and the first posed model, then per evaluation the
  * pass with k* and ∇d* in resident order, its reduce, the moments and their
  * reduce, one single-workgroup LM step — chain rule, the prior, accept or

@@ -1,7 +1,7 @@
 // capi.hip — the C-ABI of include/flashsdf.h: the context (ctx.h) and its
 // settings, the resident model, point queries and ray casts, profiling. The
 // resident cloud is cloud.hip's, the three-launch residual pass (pose -> pass
-// -> reduce) pass.hip's, mechanism iterations iterate.hip's.
+// -> reduce) pass.hip's, mechanism iterations iterate.hip's, solver loops descend.hip's.
 //
 // Ownership mirrors the reference: the cloud is held for a whole frame
 // (CostFunctor keeps sensed_points by reference, src/gradientdescent.jl:41-47)

@@ -1,6 +1,7 @@
 // ctx.h — the context behind include/flashsdf.h, shared by the host-side
 // translation units: capi.hip (context, model, queries), cloud.hip (resident
-// cloud), pass.hip (the residual pass), iterate.hip (mechanism, solver loops).
+// cloud), pass.hip (the residual pass), iterate.hip (mechanism, one iteration),
+// descend.hip (the solver loops).
 //
 // The context owns its device and pinned memory in the buffers of
 // device_buffers.h (see the rule there: a pointer is read with get() after the
@@ -18,6 +19,9 @@
 #include "device_buffers.h"
 #include "flashsdf.h"
 #include "fsdf_internal.h"
+#if FSDF_HOST_TIMES
+#include <chrono>
+#endif
 
 constexpr int kOrderEvery = FSDF_ORDER_EVERY;
 constexpr int kPoseRing = 8;
@@ -250,4 +254,28 @@ enum { kMomentsRigid = 0, kMomentsAll = 1, kMomentsSkins = 2 };
 int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who, int what = kMomentsRigid);
 int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
           double* grad_out, bool want_pp);
+// iterate.hip (the solver loops of descend.hip run on them)
+// after an iteration pass: the new cloud's first one regroups it when the auto rule says so
+int iteration_regroup(fsdf_ctx* c);
+// the host halves of one CostFunctor iteration at x around a pass: prepare = FK, RBF centres +
+// weight solve + rows upload, surface poses; finish = RBF adjoint, chain rule, regularizer
+int iteration_prepare(fsdf_ctx* c, const double* x, const char* who, bool upload = true);
+int iteration_finish(fsdf_ctx* c, const double* x, const double* accum, double* cost_out, double* grad_out,
+                     const char* who);
+
+// diagnostic builds (-DFSDF_HOST_TIMES=1): host-side clocks of the host solver
+// loop's iterations — prepare (FK, poses), launches, the wait, the chain rule —
+// summed by fsdf_value_and_gradient (iterate.hip) and printed by fsdf_descend
+// (descend.hip, stderr), to split the GPU's idle gap between iterations into
+// host work and synchronisation latency
+#if FSDF_HOST_TIMES
+extern double g_host_t[8];
+extern long g_host_n;
+static inline double host_now_us() {
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+#define HOST_STAMP(i) const double ht_##i = host_now_us()
+#else
+#define HOST_STAMP(i)
+#endif
 #pragma GCC visibility pop

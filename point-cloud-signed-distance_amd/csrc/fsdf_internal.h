@@ -262,7 +262,7 @@ size_t moments_partials_len(int64_t n, int S);
 // n > 0, moments_fit(S). d_pts: the resident cloud (precision 64 / 32; all
 // arithmetic fp64); d_moments [S][21]. A k* outside [0, S) contributes nothing.
 // skip (optional): a device flag; set, both launches return at once (the
-// evaluations a finished device LM frame still has queued, solver.hip)
+// evaluations a finished device LM frame still has queued, lm_solver.hip)
 hipError_t launch_moments(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_grad, int64_t n,
                           int S, double* d_partials, double* d_moments, hipStream_t s, const int* skip = nullptr);
 
@@ -342,9 +342,9 @@ hipError_t sort_points_spatial(const double* d_src, int64_t n, int precision, vo
 // pts.get() anew); d_perm and prior are permuted in place. Asynchronous on `st`.
 hipError_t regroup_points(DevBuf<unsigned char>& pts, int64_t n, int precision, int32_t* d_perm, uint8_t* prior,
                           SortScratch& s, hipStream_t st);
-// ---- device solver iteration (solver.hip) ------------------------------------
+// ---- device solver iteration (solver.hip, solver_common.h) ------------------------------------
 // The mechanism of a rigid scene as two device buffers built by the context
-// from fsdf_set_mechanism (iterate.hip build_solver_tree) — integers and doubles,
+// from fsdf_set_mechanism (descend.hip build_solver_tree) — integers and doubles,
 // each array at an offset — with the level schedules of the parallel FK and
 // chain rule. The solver kernels copy both buffers into LDS first, so every
 // later access in their level loops is an LDS access.
@@ -402,6 +402,37 @@ struct SolverState {
   double rate = 0.0, max_step = 0.0, tol = 0.0, n_points = 1.0, weight = 0.0;
   int limit = 0;
 };
+// descend_device's buffers. Device (doubles): x [2][nx] (slots by iteration
+// parity) | div [nx] | Rb|tb [2][12 nb] | f | RBF scenes: the weight solve's
+// state [2][9 nb + 3 rc + rm + rlu] and the row permutation [2][rm] ints; the
+// flags are a buffer of their own. carve_solver_state fills st's pointers into
+// d (null: none) and returns the doubles needed. Pinned (doubles): x [2][nx] |
+// div [nx] | f | flags [4] (as 2 doubles): x (and the divisors) are uploaded
+// from its start, and x [2][nx], f and the flags read back to their places.
+inline size_t carve_solver_state(const SolverTree& T, bool divisors, double* d, SolverState* st) {
+  const size_t nx = (size_t)T.nx, nb = (size_t)T.nb;
+  const size_t rbf_slot = T.R > 0 ? 9 * nb + 3 * (size_t)T.rc + (size_t)T.rm + (size_t)T.rlu : 0;
+  const size_t o_div = 2 * nx, o_Rb = 3 * nx, o_f = o_Rb + 24 * nb, o_rbf = o_f + 1, o_prow = o_rbf + 2 * rbf_slot;
+  if (d) {
+    st->x = d;
+    st->div = divisors ? d + o_div : nullptr;
+    st->Rb = d + o_Rb;
+    st->f = d + o_f;
+    if (T.R > 0) {
+      st->rbf = d + o_rbf;
+      st->prow = (int32_t*)(d + o_prow);
+    }
+  }
+  return o_prow + (T.R > 0 ? (size_t)T.rm + 1 : 0);
+}
+struct SolverStaging {
+  size_t div, f, flags;  // offsets in the pinned buffer (x at 0)
+  size_t total, up;      // its doubles; the doubles uploaded from its start
+};
+inline SolverStaging solver_staging(int nx, bool divisors) {
+  const size_t n = (size_t)nx;
+  return SolverStaging{2 * n, 3 * n, 3 * n + 1, 3 * n + 3, (divisors ? 3 : 1) * n};
+}
 // the step's LDS (the tree, the accumulator and the work arrays, the kernels'
 // static __shared__ included) fits one workgroup. nx = nq + 3 n_deform; ni, nd:
 // the tree blob's ints and doubles; rbf_n [R]: the skins' centre counts
@@ -418,7 +449,7 @@ hipError_t launch_solver_step(const SolverTree& T, const SolverState& st, const 
                               const LocalModel& lm, const PosedModel& pm, int precision, int it_before,
                               hipStream_t s);
 
-// ---- device Levenberg-Marquardt loop (solver.hip) ------------------------------
+// ---- device Levenberg-Marquardt loop (lm_solver.hip) ------------------------------
 // One frame's state of fsdf_descend_lm's device loop. The trial of evaluation k
 // (0-based; the frame's start x is trial 0) lies in slot k & 1 of x [2][nq],
 // its joint frames in slot k & 1 of Rb [2][12 nb] (as SolverState's); the
@@ -435,9 +466,43 @@ struct LmState {
   double max_step = 0.0, tol = 0.0, n_points = 1.0, weight = 0.0;
   int limit = 0;
 };
+// descend_lm_device's buffer, device and pinned alike (doubles): x [2][nq] |
+// x_ref [nq] | mu [nq] | lam | flags [4] (as 2 doubles) | f | xa [nq] | g [nq] |
+// H [nq][nq] | Rb|tb [2][12 nb]. carve_lm_state fills ls's pointers into d
+// (null: none; mu only with a prior) and returns the spans: the first `up`
+// doubles are uploaded (x_ref, mu, lam at these offsets), and `back` doubles
+// from lam are read back in one copy — lam | flags (at b_flags) | f (b_f) | xa
+// (b_xa).
+struct LmSpans {
+  size_t need, up, back;
+  size_t ref, mu, lam;
+  static constexpr size_t b_flags = 1, b_f = 3, b_xa = 4;
+};
+inline LmSpans carve_lm_state(int nb, int nq_, bool prior, double* d, LmState* ls) {
+  const size_t nq = (size_t)nq_;
+  const size_t o_ref = 2 * nq, o_mu = 3 * nq, o_lam = 4 * nq, o_flags = o_lam + 1, o_f = o_flags + 2, o_xa = o_f + 1,
+               o_g = o_xa + nq, o_H = o_g + nq, o_Rb = o_H + nq * nq;
+  if (d) {
+    ls->x = d;
+    ls->x_ref = d + o_ref;
+    ls->mu = prior ? d + o_mu : nullptr;
+    ls->lam = d + o_lam;
+    ls->flags = (int*)(d + o_flags);
+    ls->f = d + o_f;
+    ls->xa = d + o_xa;
+    ls->g = d + o_g;
+    ls->H = d + o_H;
+    ls->Rb = d + o_Rb;
+  }
+  return LmSpans{o_Rb + 24 * (size_t)nb, o_f, nq + 4, o_ref, o_mu, o_lam};
+}
 // the LM step's LDS (its carve and the kernel's static __shared__) fits one
-// workgroup's 64 KB, and nq one wave (the factorisation owns a row per lane)
-bool lm_solver_fits(int nb, int nq, int S);
+// workgroup's 64 KB, nq one wave (the factorisation owns a row per lane), and
+// the LM pose kernel's LDS (the tree blob of ni ints and nd doubles, the rigid
+// step's carve, its static __shared__) fits too
+bool lm_solver_fits(int nb, int nq, int S, int ni, int nd);
+// diagnostic builds (-DFSDF_SOLVER_TIMES=1): solver_times for the LM step's launches
+void lm_solver_times(unsigned long long* out);
 // After evaluation it_before (0-based) — its pass, reduce and moments: the
 // trial's wrapped objective (+ prior), accept / reject, on acceptance the
 // Gauss-Newton matrix at the trial, the end conditions in the host loop's

@@ -23,7 +23,7 @@
 #include "flashsdf.h"
 #include "gn_impl.h"
 
-// The per-element arithmetic is gn_impl.h's (the device LM loop, solver.hip,
+// The per-element arithmetic is gn_impl.h's (the device LM loop, lm_solver.hip,
 // runs the same functions in parallel): here the sequential loops over it.
 using fsdf::gn::joint_rows;
 using fsdf::gn::joint_width;

@@ -1,7 +1,7 @@
 // gn_impl.h — the per-element arithmetic of the Gauss-Newton matrix and of the
 // damped (Levenberg-Marquardt) step, shared by the host entry points
 // (gauss_newton.cpp fsdf_gauss_newton_matrix / fsdf_lm_step) and the device LM
-// loop (solver.hip lm_step_kernel). As kin_impl.h: every function is one
+// loop (lm_solver.hip lm_step_kernel). As kin_impl.h: every function is one
 // element's work with a fixed operation order, so the host's sequential loops
 // and the device's parallel ones give the same bits (-ffp-contract=off in both
 // translation units; device sqrt and division are correctly rounded).

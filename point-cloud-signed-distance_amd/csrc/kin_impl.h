@@ -1,7 +1,7 @@
 // kin_impl.h — the per-body arithmetic of forward kinematics, the surface
 // poses and the chain rule, shared by the host loop (kinematics.cpp, iterate.hip
 // iteration_prepare / fsdf_config_gradient) and the device solver step
-// (solver.hip). Every function is one body's (or one surface's) work with a
+// (solver_common.h). Every function is one body's (or one surface's) work with a
 // fixed operation order, so the host's sequential loop over bodies and the
 // device's level-parallel loop produce the same bits (both translation units
 // are built with -ffp-contract=off; device sqrt and division are correctly

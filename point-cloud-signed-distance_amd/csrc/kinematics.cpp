@@ -7,7 +7,7 @@
 // is one loop over the bodies in topological order (parent[b] < b).
 //
 // The per-body arithmetic (joint motion, composition, chain rule) is
-// kin_impl.h's, shared with the device solver step (solver.hip) so that the
+// kin_impl.h's, shared with the device solver step (solver_common.h) so that the
 // host and device iterations agree bit for bit.
 
 #include <math.h>
@@ -45,7 +45,7 @@ extern "C" int fsdf_tree_transforms(int32_t nb, const int32_t* parent, const int
 // (children before parents: reverse topological order), then per joint with
 // the world motion subspace of its frame before the motion (Rb, tb of
 // fsdf_tree_transforms; kin_impl.h joint_gradient). F, M are about the world
-// origin. The device solver step (solver.hip) adds in the same order.
+// origin. The device solver step (solver_common.h) adds in the same order.
 extern "C" int fsdf_config_gradient(int32_t nb, const int32_t* parent, const int32_t* kind, const int32_t* qoff,
                                     const double* axis, const double* Rb, const double* tb, const double* q,
                                     int32_t nsurf, const int32_t* surface_body, const double* surface_wrench,

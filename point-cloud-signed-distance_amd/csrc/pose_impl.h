@@ -2,7 +2,7 @@
 // screening pairs, stage images, vertices, bounding spheres / boxes and
 // certificate scales of every hull from the surfaces' 3x4 poses. One function
 // per work item, shared by the pose kernels (sdf_kernels.hip) and the device
-// solver step (solver.hip), which poses the next pass's model itself.
+// solver step (solver.hip, solver_common.h), which poses the next pass's model itself.
 #pragma once
 
 #include <hip/hip_runtime.h>

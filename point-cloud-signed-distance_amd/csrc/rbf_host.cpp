@@ -17,7 +17,7 @@
 #include <cstring>
 
 #include "flashsdf.h"
-#include "rbf_impl.h"  // the arithmetic, shared with the device solver step (solver.hip)
+#include "rbf_impl.h"  // the arithmetic, shared with the device solver step (solver_rbf.h)
 
 using namespace fsdf::rbf;
 

@@ -1,6 +1,6 @@
 // rbf_impl.h — the arithmetic of the RBF skins' per-pass weight solve and its
 // adjoint, shared by the host (rbf_host.cpp fsdf_rbf_solve / fsdf_rbf_adjoint)
-// and the device solver step (solver.hip), as kin_impl.h shares the FK. Every
+// and the device solver step (solver_rbf.h), as kin_impl.h shares the FK. Every
 // function is one entry's / one row's / one centre's work with a fixed
 // operation order, so the host's sequential loops and the device's
 // workgroup-parallel ones produce the same bits (both are built with
@@ -11,7 +11,7 @@
 // A_ij = |c_i - c_j|^3, P_i = (1, c_iᵀ), u = (w, a, b), rhs = (values, 0).
 // PA = LU with partial pivoting: the host swaps rows in place (lu_factor); the
 // device keeps the rows where they are, swaps a row map, searches the pivot
-// across a wave's lanes (the same index: solver.hip rbf_factor) and applies
+// across a wave's lanes (the same index: solver_rbf.h rbf_factor) and applies
 // lu_multiplier / lu_eliminate / subst_term per entry.
 #pragma once
 #include <math.h>

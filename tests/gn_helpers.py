@@ -107,3 +107,60 @@ class OracleCost:
         c, gq, (d, k, g) = self.value_and_gradient(x)
         A = self.m.mechanism.gauss_newton_matrix_numpy(x, self.sb, moments_numpy(self.pts, g, k, len(self.sb)))
         return c, gq, 2.0 * A
+
+
+def branching_scene(name, n=4096):
+    """(manipulator, cloud, start) of a tree that branches below the root, one
+    box per body — the scenes whose subtree sums run level by level:
+      hand  a revolute base link carries a revolute palm, the palm three fingers
+            of two links each (8 bodies; the middle finger's first joint is
+            Fixed, so a body without coordinates lies inside the ancestor
+            walks): three parents at the widest height, the one-wave form
+      comb  a revolute spine carries 11 revolute teeth of two revolute leaves
+            each (34 bodies, 34 coordinates): 11 parents at one height, more
+            than one wave's ten, so a barrier per level
+    The boxes are apart at the cloud's configuration (angles within 0.2 rad);
+    the start is that configuration perturbed by sigma = 0.05 rad."""
+    from flash import Models, synthetic
+    from flash.core import ConvexGeometry, Manipulator
+    from flash.geometry import Transform
+    from flash.mechanism import Fixed, Mechanism, Revolute
+
+    def at(x, y, z):
+        return Transform(np.eye(3), np.array([x, y, z], np.float64))
+
+    mech, surfaces = Mechanism("world"), []
+
+    def link(parent, joint, where, label, half, centre):
+        b = mech.attach(parent, joint, where, label)
+        surfaces.append(ConvexGeometry(Models.box_hull(half), b, at(*centre), label))
+        return b
+
+    if name == "hand":
+        base = link(0, Revolute([0, 0, 1], "base_joint"), None, "base", (0.15, 0.15, 0.05), (0, 0, 0.05))
+        palm = link(base, Revolute([0, 1, 0], "palm_joint"), at(0, 0, 0.15), "palm", (0.2, 0.05, 0.1), (0, 0, 0.15))
+        first = []
+        for i, x in enumerate((-0.15, 0.0, 0.15)):
+            joint = Fixed(f"finger{i}_joint1") if i == 1 else Revolute([1, 0, 0], f"finger{i}_joint1")
+            first.append(link(palm, joint, at(x, 0, 0.28), f"finger{i}_link1", (0.03, 0.03, 0.08), (0, 0, 0.1)))
+        for i, b in enumerate(first):
+            link(b, Revolute([1, 0, 0], f"finger{i}_joint2"), at(0, 0, 0.2), f"finger{i}_link2", (0.03, 0.03, 0.08),
+                 (0, 0, 0.1))
+        seed = 51
+    elif name == "comb":
+        spine = link(0, Revolute([0, 0, 1], "spine_joint"), None, "spine", (1.2, 0.04, 0.04), (0, 0, 0))
+        teeth = [link(spine, Revolute([1, 0, 0], f"tooth{i}_joint"), at(-1.0 + 0.2 * i, 0, 0.06), f"tooth{i}",
+                      (0.05, 0.03, 0.08), (0, 0, 0.1)) for i in range(11)]
+        for i, b in enumerate(teeth):
+            for side, y in enumerate((-0.07, 0.07)):
+                link(b, Revolute([0, 1, 0], f"leaf{i}_{side}_joint"), at(0, y, 0.2), f"leaf{i}_{side}",
+                     (0.04, 0.025, 0.05), (0, 0, 0.07))
+        seed = 61
+    else:
+        raise ValueError(name)
+    m = Manipulator(mech, surfaces)
+    nq = mech.num_positions
+    q_true = np.random.default_rng(seed).uniform(-0.2, 0.2, nq)
+    pts = synthetic.depth_cloud(m, q_true, n, seed=seed + 1)
+    x0 = q_true + np.random.default_rng(seed + 2).normal(0.0, 0.05, nq)
+    return m, pts, x0

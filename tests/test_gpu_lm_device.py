@@ -1,5 +1,5 @@
 """GPU: the device-resident Levenberg-Marquardt loop (fsdf_set_lm_solver,
-csrc/solver.hip lm_step_kernel / lm_pose_kernel) against fsdf_descend_lm's host
+csrc/lm_solver.hip lm_step_kernel / lm_pose_kernel) against fsdf_descend_lm's host
 loop — x, f, the evaluation count and the final damping bit for bit, with and
 without the prior of fsdf_set_lm_prior — its refusals, its buffer discipline
 and its way through estimate_state."""
@@ -156,6 +156,56 @@ def test_device_loop_equals_host_loop(scenes, scene, with_prior):
               f"damping {host[3]:.1e}")
         assert host[2] == len(trace) > len(accepted)  # (on every scene: a rejected trial)
         assert _same(host, dev), (host, dev)
+    finally:
+        ctx.close()
+
+
+# At this damping the host runs below reject trials: `comb` 4 of 8 in its first
+# frame and 7 in the warm-started one; `hand` from the scene's own start accepts
+# all 16 with the prior (each frame's reference moves with it), so its start is
+# this much further off (rad, seed 7): 4 of the second frame's 8 rejected with
+# the prior, 6 without.
+BRANCHING_DAMPING = 1e-9
+BRANCHING_START_SIGMA = {"hand": 0.15, "comb": 0.0}
+
+
+@pytest.mark.parametrize("with_prior", [False, True], ids=["plain", "prior"])
+@pytest.mark.parametrize("scene", ["hand", "comb"])
+def test_device_loop_equals_host_loop_on_branching_trees(scene, with_prior):
+    """Trees that branch below the root (gn_helpers.branching_scene): the
+    chain rule's level-ordered subtree sums and the matrix entries' ancestor
+    walks between coordinates of different branches (and, in `hand`, through a
+    body without coordinates), which no set of chains runs. Two frames of 8
+    evaluations on both loops — from the perturbed start, then warm-started at
+    that frame's end point, where Gauss-Newton steps fit the noise — x, f, the
+    evaluations and the damping bit for bit; the host runs reject a trial."""
+    from gn_helpers import branching_scene
+    m, pts, x0 = branching_scene(scene)
+    x0 = x0 + np.random.default_rng(7).normal(0.0, 1.0, len(x0)) * BRANCHING_START_SIGMA[scene]
+    mu = _prior(len(x0)) if with_prior else None
+    n = float(len(pts))
+    ctx = _fresh(m)
+    try:
+        ctx.set_lm_prior(mu)
+        ctx.set_points(pts)
+        for frame in ("start", "warm start"):
+            ctx.value_and_gradient(x0)  # (the cloud's first pass: both loops start from the same layout)
+            trace, accepted = _python_trace(ctx, x0, mu, n, 8, BRANCHING_DAMPING)
+            res = []
+            for mode in (False, "require"):
+                ctx.set_lm_solver(mode)
+                res.append(ctx.descend_lm(x0, 8, BRANCHING_DAMPING, 0.5, 0.0, n))
+            ctx.set_lm_solver(False)
+            host, dev = res
+            print(f"{scene} prior={with_prior} {frame}: evaluations {host[2]}, accepted {len(accepted)}, "
+                  f"f {host[1]:.6e}, damping {host[3]:.1e}")
+            assert host[2] == len(trace) == 8
+            assert _same(host, dev), (host, dev)
+            if frame == "start":
+                assert not np.array_equal(host[0], x0)
+            else:
+                assert len(trace) > len(accepted)  # (a rejected trial: the reject branch is compared)
+            x0 = host[0].copy()
     finally:
         ctx.close()
 

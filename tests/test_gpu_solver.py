@@ -80,6 +80,42 @@ def test_device_loop_bit_identical_to_host_loop(name, n):
     ctx.set_solver(True)  # (the default)
 
 
+@pytest.mark.parametrize("name", ["hand", "comb"])
+def test_device_loop_on_branching_trees(name):
+    """Trees that branch below the root (gn_helpers.branching_scene): the
+    subtree sums run level by level — `hand` in one wave, `comb` (11 parents at
+    one height) with a barrier per level — where every other scene here is a
+    set of chains. x, f and the iteration count of the required device loop
+    equal the host loop's: a run that never stops, and one with divisors and a
+    tolerance just above |g| at the host loop's third iterate, which stops
+    there or earlier."""
+    from flash.gradientdescent import CostFunctor
+    from gn_helpers import branching_scene
+    m, pts, x0 = branching_scene(name)
+    cf = CostFunctor(m, pts)
+    ctx = cf.ctx
+    n = float(len(pts))
+    div = np.linspace(1.0, 1.5, len(x0))
+    ctx.set_solver(False)
+    x3, _, its = cf.descend(x0, 3, 2.0, 0.05, 0.0, div, n)
+    assert its == 3
+    g = cf.value_and_gradient(x3)[1] / n / div
+    tol = float(np.sqrt(sum(float(v) * float(v) for v in g))) * 1.000001
+    for tol_, limit, rate, div_ in ((0.0, 7, 0.5, None), (tol, 8, 2.0, div)):
+        res = []
+        for dev_loop in (False, "require"):
+            ctx.set_solver(dev_loop)
+            res.append(cf.descend(x0, limit, rate, 0.05, tol_, div_, n))
+        (xa, fa, ia), (xb, fb, ib) = res
+        print(f"{name} tolerance {tol_:.3e}: iterations {ia}, f {fa:.6e}")
+        assert ia == ib, (ia, ib)
+        assert fa == fb, (fa, fb)
+        assert np.array_equal(xa, xb), np.abs(xa - xb).max()
+        assert not np.array_equal(xa, x0)
+        assert ib == limit if tol_ == 0.0 else 1 < ib < limit
+    ctx.set_solver(True)  # (the default)
+
+
 def test_device_loop_refuses_bad_configuration():
     """A zero quaternion fails FK on the device as on the host (FSDF_ERR_ARG),
     and the context stays usable."""

@@ -1,6 +1,6 @@
 """GPU: the device solver loop of fsdf_descend on scenes with RBF skins and
-deformations (csrc/solver.hip with csrc/rbf_impl.h; fsdf_set_solver modes 3
-"all" and 4 "require-all").
+deformations (csrc/solver.hip, csrc/solver_rbf.h with csrc/rbf_impl.h;
+fsdf_set_solver modes 3 "all" and 4 "require-all").
 
 The step does on the device what the host loop does around every pass — the
 adjoint of the skins' weight solve, the body wrenches, the deformation
