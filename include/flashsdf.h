@@ -707,7 +707,9 @@ int fsdf_chunk_costs(fsdf_ctx* ctx, uint32_t* costs_out, int64_t* count_out);
  *   timeline build, tools/wave_times.py)
  *   [19] screened plane maxima that fell back to the full fp64 scan (per
  *   wave) [20] evaluations rejected early by the screen [21] descent-walk
- *   steps (per wave) [22..23] reserved (0). 24 counters. */
+ *   steps (per wave) [22] waves on the seed-first path (their candidates
+ *   in [8] are those left by the cull after the seeds) [23] reserved (0).
+ *   24 counters. */
 int fsdf_kernel_stats(fsdf_ctx* ctx, int32_t enable, uint64_t* counters_out);
 
 #ifdef __cplusplus

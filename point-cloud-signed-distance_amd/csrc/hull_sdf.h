@@ -260,7 +260,8 @@ __device__ __forceinline__ bool cert_step(T px, T py, T pz, int f, int reg, cons
 // fp64 plane values h_f = n_f·p − d_f, from an fp32 pass over all faces plus
 // an fp64 pass over ONE batch of 8.
 //   Screen: h'_f = n'·q − d'' in packed fp32 (v_pk_fma_f32: two faces per
-//   instruction, plane pairs read through the scalar unit), q = fl32(p − c),
+//   instruction, plane pairs staged in LDS and read with ds_read_b128),
+//   q = fl32(p − c),
 //   c the hull's sphere centre, with |h'_f − h_f| <= E = 16u (|q|_1 + r)
 //   (u = 2^-24; |n_i| <= 1 and |d − n·c| <= r). Per batch of 8 faces the
 //   maximum b; b1 = best batch maximum, b2 = best over the other batches.

@@ -52,7 +52,18 @@ __global__ __launch_bounds__(NB) __attribute__((
   constexpr int kParts = HPART ? NPART : 1;
   constexpr int kChunkStride = NB / kParts;  // points per logical block
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  // The wave index is wave-uniform, and readfirstlane tells the compiler so:
+  // the wave's stage and row addresses then stay out of the vector registers,
+  // which scene_eval fills to the budget (the bench variant spilled without
+  // it once the seed-first path was added). It is a register-budget measure
+  // only, checked per variant against the resource-usage remarks of `make
+  // asm`: 1 to 15 VGPRs fewer everywhere except the brute-force variants of
+  // more than 64 hulls (!CULL, !RBF, SLOTS > 1), which took 2 more and
+  // therefore keep the lane value. When this line or scene_eval changes,
+  // re-check the VGPRs / ScratchSize / Occupancy lines of every pass_kernel
+  // variant (profiles/r07/seed_first/resource_usage_head.txt is the record).
+  const int wave = (SLOTS == 1 || CULL || RBF) ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)
+                                                : (int)(threadIdx.x >> 6);
   // (wave-uniform: readfirstlane keeps the hull mask and the loops scalar)
   const int part = HPART ? __builtin_amdgcn_readfirstlane(wave % kParts) : 0;  // (HPART) this wave's hull residue
   const int cw = HPART ? __builtin_amdgcn_readfirstlane(wave / kParts) : wave;  // the block's chunk this wave works on
@@ -312,6 +323,8 @@ __global__ __launch_bounds__(kPassBlock) __attribute__((amdgpu_waves_per_eu(kPas
     const T* __restrict__ pts, int64_t n, PassModel<T> m, PassOutputs out, ChunkOutputs co) {
   if (out.skip && *out.skip) return;
   const int lane = threadIdx.x & 63;
+  // (a lane value here: told wave-uniform as in pass_kernel, the kernel took 8
+  // registers fewer and ran 1.3 % slower at 2^17 points)
   const int wave = threadIdx.x >> 6;
   HullRow* ht = (HullRow*)fsdf_lds;
   char* stages = (char*)(ht + m.K + 1);

@@ -63,18 +63,62 @@ __device__ __forceinline__ void scene_eval(T px, T py, T pz, bool valid, const P
     cand[s] = left >= 64 ? ~0ull : (left > 0 ? (1ull << left) - 1 : 0ull);
   }
   uint64_t tw = wt_now();
-  // the wave's bounding sphere (bbox centre, half diagonal) over the valid
-  // lanes: precomputed per resident chunk at set_points (pose-independent,
-  // the same arithmetic) or computed here
   pxf = (float)px; pyf = (float)py; pzf = (float)pz;
-  WaveSphere ws;
-  if (cws) {
-    const F4 v = *cws;
-    ws = WaveSphere{v[0], v[1], v[2], v[3]};
-  } else {
-    ws = wave_sphere(pxf, pyf, pzf, valid);
+  // the point's nearest surface in the previous pass over this cloud, when
+  // known (PassOutputs::prior_in), is its seed: tracking passes move the model
+  // little, so it is usually this pass's nearest too, and `best` is tight after
+  // the first evaluation (any seed gives the same bits)
+  const bool prior_ok = CULL && !RBF && SLOTS == 1 && prior >= 0 && prior < K && ((partmask >> (prior & 63)) & 1);
+  // Seed-first path (wave-uniform): every valid lane of the wave has a usable
+  // prior (and the chunk its precomputed sphere, as every resident cloud's
+  // has). No candidate loop and no wave-level cull here: the seed is the prior,
+  // ub = |p - c_prior| (a true upper bound of d*, one table row per lane), every
+  // hull stays a candidate until the seeds are evaluated, and ONE wave-level
+  // cull then runs against the lanes' tight bests (in the loop below). Every
+  // other wave — a cloud's first pass, a lane whose prior is missing or outside
+  // the wave's part, the hull-partitioned tiers — runs Phase A as before.
+  constexpr bool kSeedFirst = CULL && !RBF && SLOTS == 1;
+  bool seed_first = false;
+  if constexpr (kSeedFirst) {
+    const uint64_t vm = __ballot(valid);
+    seed_first = cws != nullptr && vm != 0 && __ballot(prior_ok) == vm;
   }
-  if (CULL) {
+  // the wave-level cull's test of hull (64 s + lane) against the upper bound
+  // `u` of every valid lane's d*: with the wave's points inside the sphere
+  // w = (c_w, r_w) and D_k = |c_w - c_k|, every point of the wave has
+  // d_k >= D_k - r_w - r_k and d_k >= the box bound at c_w (1-Lipschitz) minus
+  // r_w, so a hull one of whose lower bounds exceeds u by the fp32 margin is
+  // needed by no lane
+  // (its fp32 rounding margin, >= 1e-5 x every magnitude in the test; the
+  // seed-first cull below takes the same margin but runs the test through the
+  // loop's needs_at site rather than a second inlined copy of the box test,
+  // which cost registers at the budget)
+  auto wave_margin = [&](float wx, float wy, float wz, float wr, float u) -> float {
+    return 1e-5f * (1.0f + fabsf(wx) + fabsf(wy) + fabsf(wz) + smax + 4.0f * wr + 2.0f * fabsf(u));
+  };
+  auto wave_cull_at = [&](const WaveSphere& w, int s, float Dks, float u) -> uint64_t {
+    const float mrgw = wave_margin(w.x, w.y, w.z, w.r, u);
+    const int k = 64 * s + lane;
+    const HullRow& h = ht[k < K ? k : 0];
+    const bool c = (k < K) & (Dks - w.r - h.sphere[3] <= u + mrgw) & box_within(h, w.x, w.y, w.z, u + mrgw + w.r);
+    return __ballot(c);
+  };
+  if (CULL && seed_first) {
+    kseed = prior_ok ? prior : 0;
+    const F4 sp = ht[kseed].sphere;
+    const float dx = pxf - sp[0], dy = pyf - sp[1], dz = pzf - sp[2];
+    ub2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+  } else if (CULL) {
+    // the wave's bounding sphere (bbox centre, half diagonal) over the valid
+    // lanes: precomputed per resident chunk at set_points (pose-independent,
+    // the same arithmetic) or computed here
+    WaveSphere ws;
+    if (cws) {
+      const F4 v = *cws;
+      ws = WaveSphere{v[0], v[1], v[2], v[3]};
+    } else {
+      ws = wave_sphere(pxf, pyf, pzf, valid);
+    }
     // Wave-level culling, one hull per lane: with the wave's points inside the
     // sphere (c_w, r_w) and D_k = |c_w - c_k|, every point of the wave has
     // d_k >= D_k - r_w - r_k and d_k <= D_k + r_w, so a hull whose lower bound
@@ -94,15 +138,9 @@ __device__ __forceinline__ void scene_eval(T px, T py, T pz, bool valid, const P
       }
     }
     ubw = wave_minmax<false>(ubw);
-    const float mrgw = 1e-5f * (1.0f + fabsf(cwx) + fabsf(cwy) + fabsf(cwz) + smax + 4.0f * rw + 2.0f * ubw);
     // ... and so does one whose box bound at c_w (1-Lipschitz) minus r_w does
 #pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-      const int k = 64 * s + lane;
-      const HullRow& h = ht[k < K ? k : 0];
-      const bool c = (k < K) & (Dk[s] - rw - h.sphere[3] <= ubw + mrgw) & box_within(h, cwx, cwy, cwz, ubw + mrgw + rw);
-      cand[s] = __ballot(c);
-    }
+    for (int s = 0; s < SLOTS; ++s) cand[s] = wave_cull_at(ws, s, Dk[s], ubw);
     if (count_events(stats) && lane == 0) {
       unsigned long long nc = 0;
 #pragma unroll
@@ -131,11 +169,7 @@ __device__ __forceinline__ void scene_eval(T px, T py, T pz, bool valid, const P
       }
     }
   }
-  // the point's nearest surface in the previous pass over this cloud, when
-  // known (PassOutputs::prior_in), is its seed instead: tracking passes move
-  // the model little, so it is usually this pass's nearest too, and `best` is
-  // tight after the first evaluation (any seed gives the same bits)
-  const bool prior_ok = CULL && !RBF && SLOTS == 1 && prior >= 0 && prior < K && ((partmask >> (prior & 63)) & 1);
+  // (a lane's prior, where it has one, replaces the best-first seed)
   if (prior_ok) kseed = prior;
   const float ub = __builtin_sqrtf(ub2);
   tw = wt_add(4, tw);
@@ -185,11 +219,6 @@ __device__ __forceinline__ void scene_eval(T px, T py, T pz, bool valid, const P
     }
     return b;
   };
-  auto needs = [&](int k) -> bool {
-    if (!CULL) return valid;
-    const T b = bound_now();
-    return valid & needs_at(ht[k], pxf, pyf, pzf, fminf(ub, (float)b) + mrg);
-  };
   // evaluations may run out of index order: ties keep the smaller k
 #if FSDF_WAVE_TIMES
   uint64_t wt_slowk = 0;  // hulls whose evaluation ran this lane's search
@@ -227,45 +256,103 @@ __device__ __forceinline__ void scene_eval(T px, T py, T pz, bool valid, const P
   // evaluation per distinct seed in the wave, so that `best` is tight), then
   // the remaining candidates in index order (Phase C).
   uint64_t pend = (CULL && K > 0) ? __ballot(valid && (lb_min < __builtin_huge_valf() || prior_ok)) : 0ull;
-  int slot = -1;      // Phase C slot; -1 while seeds are pending
+  int slot = seed_first ? -2 : -1;  // Phase C slot; -1 while seeds are pending (-2: and the seed-first cull)
   uint64_t cm = 0ull;  // Phase C candidates left in `slot`
   for (;;) {
-    int k;
-    bool need;
+    // each turn tests ONE hull row per lane with needs_at (one site: the seed
+    // and Phase C turns test the turn's hull k at the lane's point against the
+    // lane's bound, the seed-first cull turn tests hull `lane` at the chunk's
+    // centre against the wave's bound)
+    int k = 0, row;
+    float qx, qy, qz, tb;
+    bool cull_turn = false;
+#if FSDF_WAVE_TIMES
+    uint64_t tw_need = 0;
+#endif
     if (pend) {
       k = __builtin_amdgcn_readfirstlane(__shfl(kseed, __builtin_ctzll(pend), 64));
       pend &= ~__ballot(valid && kseed == k);
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s)
         if ((k >> 6) == s) done[s] |= 1ull << (k & 63);
-      need = needs(k);
       if (count_events(stats) && lane == 0) atomicAdd(stats + 5, 1ull);
       wt_count(4, 1);
-      // a seed the earlier seeds' results have ruled out for every lane (its
-      // bit is in `done`; bounds only tighten, so Phase C would skip it too):
-      // no staging, no screen (2^17: 0.0464 -> 0.0454 ms pass)
-      if (!__any(need)) continue;
     } else {
-      while (!cm && slot < SLOTS - 1) {
-        ++slot;
+      if constexpr (kSeedFirst) cull_turn = slot == -2;
+      if (!cull_turn) {
+        while (!cm && slot < SLOTS - 1) {
+          ++slot;
 #pragma unroll
-        for (int s = 0; s < SLOTS; ++s)
-          if (s == slot) cm = cand[s] & ~done[s] & partmask;
-      }
-      if (!cm) break;
-      k = 64 * slot + __builtin_ctzll(cm);
-      cm &= cm - 1;
+          for (int s = 0; s < SLOTS; ++s)
+            if (s == slot) cm = cand[s] & ~done[s] & partmask;
+        }
+        if (!cm) break;
+        k = 64 * slot + __builtin_ctzll(cm);
+        cm &= cm - 1;
 #if FSDF_WAVE_TIMES
-      const uint64_t tw_need = wt_now();
-      need = needs(k);
-      const bool any_need = __any(need);
-      wt_count(11, wt_now() - tw_need);
-      if (!any_need) continue;
-#else
-      need = needs(k);
-      if (!__any(need)) continue;
+        tw_need = wt_now();
 #endif
+      }
     }
+    if (cull_turn) {
+      // seed-first: the one wave-level cull, after the seeds, the existing test
+      // (D_k - r_w - r_k and the box bound at c_w minus r_w, in needs_at's
+      // sqrt-free form) against bw, the worst valid lane's min(ub, best), with
+      // mrgw's margin (+inf while a lane has no finite best: nothing is culled)
+      slot = -1;
+      // (the chunk's sphere is read here, not before the seeds: four registers
+      // live through the evaluations spilled at the budget. The empty asm makes
+      // the pointer opaque so the compiler cannot carry an earlier load over; it
+      // changes no value. Both this and the barrier below exist for the register
+      // budget alone: after a compiler update or a change here, re-check
+      // `make asm`'s resource-usage lines of pass_kernel<double, 1, true, false,
+      // true, false, 256, 4> and planned_pass_kernel<double, true> — VGPRs <=
+      // 128, ScratchSize 0, Occupancy 4 — and drop a barrier that no longer pays)
+      uint32_t cwl = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)cws);
+      uint32_t cwh = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)cws >> 32));
+      asm volatile("" : "+s"(cwl), "+s"(cwh));
+      const F4 w = *(const F4*)(((uintptr_t)cwh << 32) | cwl);
+      const float bw = wave_minmax<true>(valid ? fminf(ub, (float)bound_now()) : -__builtin_huge_valf());
+      const float mrgw = wave_margin(w[0], w[1], w[2], w[3], bw);
+      row = lane < K ? lane : 0;
+      qx = w[0]; qy = w[1]; qz = w[2];
+      tb = bw + mrgw + w[3];
+    } else {
+      // hull k is needed by a lane unless its lower bound exceeds min(ub, best)
+      // by more than the fp32 rounding margin
+      row = k;
+      if constexpr (kSeedFirst) {
+        // (the fp32 point converted again per test — three conversions — rather
+        // than three more registers live through the evaluations; the empty asm
+        // keeps the compiler from hoisting them back — see the note above on
+        // what to re-check)
+        T tx = px, ty = py, tz = pz;
+        asm volatile("" : "+v"(tx), "+v"(ty), "+v"(tz));
+        qx = (float)tx; qy = (float)ty; qz = (float)tz;
+      } else {
+        qx = pxf; qy = pyf; qz = pzf;
+      }
+      tb = fminf(ub, (float)bound_now()) + mrg;
+    }
+    bool need = CULL ? needs_at(ht[row], qx, qy, qz, tb) : true;
+    if (cull_turn) {
+      cand[0] = __ballot(need & (lane < K));
+      if (count_events(stats) && lane == 0) {
+        atomicAdd(stats + 8, (unsigned long long)__builtin_popcountll(cand[0]));
+        atomicAdd(stats + 22, 1ull);
+      }
+      continue;
+    }
+    need &= valid;
+    // (a seed the earlier seeds' results have ruled out for every lane — its
+    // bit is in `done`; bounds only tighten, so Phase C would skip it too —
+    // takes no staging and no screen either: 2^17 0.0464 -> 0.0454 ms pass,
+    // DESIGN §7)
+    const bool any_need = __any(need);
+#if FSDF_WAVE_TIMES
+    if (tw_need) wt_count(11, wt_now() - tw_need);
+#endif
+    if (!any_need) continue;
     evaluate(k, need);
   }
 #if FSDF_WAVE_TIMES

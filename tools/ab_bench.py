@@ -4,7 +4,10 @@
 rounds, and prints the pass-kernel mean (HIP events), the step and the measured
 prefetched frame (bench measured_frame, unless --no-full-iteration) per build.
 
-    python tools/ab_bench.py ab/libA.so ab/libB.so [--rounds 3] [-- bench args]
+    python tools/ab_bench.py ab/libA.so ab/libB.so [--rounds 3] [--jsonl FILE] [-- bench args]
+
+--jsonl appends every run's full result line (with "arm" and "round" added);
+the summary gives the minimum, the median and the range over the rounds.
 """
 import json
 import os
@@ -25,6 +28,11 @@ def main():
         i = argv.index("--rounds")
         rounds = int(argv[i + 1])
         del argv[i:i + 2]
+    jsonl = None
+    if "--jsonl" in argv:
+        i = argv.index("--jsonl")
+        jsonl = argv[i + 1]
+        del argv[i:i + 2]
     libs = argv
     res = {lib: [] for lib in libs}
     for r in range(rounds):
@@ -38,9 +46,12 @@ def main():
                 print(f"{lib}: FAILED rc={p.returncode}\n{p.stderr[-2000:]}", flush=True)
                 return 1
             j = json.loads(line[-1])
+            if jsonl:
+                with open(jsonl, "a") as f:
+                    f.write(json.dumps(dict(j, arm=os.path.basename(lib), round=r)) + "\n")
             mf = (j.get("measured_frame") or j["config"].get("measured_frame") or {}).get("device_loop_prefetched", {})
             res[lib].append((j["roofline"]["kernel_ms"], j["ms_per_step"], mf.get("frame_ms", float("nan")),
-                             mf.get("set_points_ms", float("nan"))))
+                             mf.get("set_points_ms", float("nan")), j["value"]))
             print(f"round {r} {os.path.basename(lib)}: pass {j['roofline']['kernel_ms']:.4f} ms, "
                   f"step {j['ms_per_step']:.4f} ms, prefetched frame {res[lib][-1][2]:.4f} ms "
                   f"(ingest {res[lib][-1][3]:.4f})", flush=True)
@@ -48,6 +59,14 @@ def main():
     for lib, v in res.items():
         print(f"  {os.path.basename(lib):32s} pass {min(x[0] for x in v):.4f} ms  step {min(x[1] for x in v):.4f} ms  "
               f"frame {min(x[2] for x in v):.4f} ms  ingest {min(x[3] for x in v):.4f} ms")
+    print("summary (median [min .. max] over rounds):")
+    for lib, v in res.items():
+        cols = []
+        for name, c in (("value", 4), ("step ms", 1), ("pass ms", 0), ("frame ms", 2)):
+            xs = sorted(x[c] for x in v)
+            med = xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2])
+            cols.append(f"{name} {med:.5g} [{xs[0]:.5g} .. {xs[-1]:.5g}]")
+        print(f"  {os.path.basename(lib):24s} " + "  ".join(cols))
     return 0
 
 
