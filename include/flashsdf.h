@@ -421,6 +421,69 @@ int fsdf_descend_lm(fsdf_ctx* ctx, double* x, int32_t iteration_limit, double da
                     double tolerance, double n_points, double* value_out, int32_t* iterations_out,
                     double* damping_out);
 
+/* ---- robust point losses -------------------------------------------------------
+ * The cost Σ d*(p)² gives a far point — a depth outlier, a point of another
+ * object — a pull that grows with its distance. A loss (kind, scale c > 0)
+ * bounds it. It is given by its weight w(d) = ρ′(d) / (2d), with ρ(d) = d² near
+ * zero (one definition and operation order: csrc/robust_impl.h, restated in
+ * numpy by flash/robust.py):
+ *   FSDF_LOSS_SQUARE  w = 1, ρ = d² (the default: no loss).
+ *   FSDF_LOSS_HUBER   |d| <= c: w = 1, ρ = d²; else w = c / |d|, ρ = 2c|d| − c².
+ *   FSDF_LOSS_TUKEY   u = d / c; |d| < c: w = (1 − u²)², ρ = (c²/3)(1 − (1 − u²)³);
+ *                     else w = 0 exactly, ρ = c²/3.
+ * With v = (∇d*, p × ∇d*), per surface k over the points with k*(p) = k the
+ * robust objective and its Gauss-Newton (IRLS) model are: cost Σ ρ(d*); wrench
+ * (F_k, M_k) = Σ 2 w d* v, in the accumulator's slots and sign; moments
+ * Σ w v vᵀ (21 entries, the order of fsdf_gauss_newton_matrix); W_k = Σ w, the
+ * surface's effective inlier count. H = 2 Σ_k JᵀM_kJ stays positive
+ * semi-definite: the second-order term of ρ is dropped. They are reduced on the
+ * device by a launch of its own after the pass (csrc/robust.hip: the design of
+ * the moments' reduction above, no floating-point atomics, bit-identical from
+ * run to run for a given cloud layout), from the pass's k*, d* and ∇d* in
+ * resident order; all arithmetic fp64, an fp32 context's pass outputs as
+ * stored. Hull-only scenes of at most 282 surfaces (the workgroup's tables in
+ * 64 KB of LDS; fsdf_set_surfaces itself holds a scene to 256); beyond,
+ * FSDF_ERR_STATE.
+ *
+ * fsdf_set_loss: a context setting, kept over model and cloud swaps; only
+ * FSDF_LOSS_SQUARE clears it (its scale is ignored). An unknown kind, or a
+ * Huber / Tukey scale that is not finite and > 0, is FSDF_ERR_ARG.
+ * fsdf_get_loss reads it back (either output may be NULL).
+ *
+ * fsdf_eval_robust: fsdf_eval's pass over the resident cloud, then the sums
+ * above under the context's loss. accum_out [1 + 6S] in fsdf_eval's layout:
+ * [0] = cost = Σρ, the surfaces' sums added in surface order; then every
+ * surface's wrench. moments_out [S][21] and weight_out [S] (W_k); every output
+ * may be NULL. Synchronous; needs no mechanism; a scene with an RBF skin is
+ * FSDF_ERR_STATE; a cloud of no points gives exact zeros. With
+ * FSDF_LOSS_SQUARE set it returns the least-squares sums as this reduction
+ * forms them: fsdf_eval_moments' cost, wrench and moments to rounding.
+ *
+ * With a loss other than FSDF_LOSS_SQUARE set, on a rigid scene (no RBF skin,
+ * no deformation; others: FSDF_ERR_STATE from the four calls below):
+ * fsdf_value_and_gradient and fsdf_value_gradient_hessian evaluate the robust
+ * objective — the same FK, chain rule and fsdf_gauss_newton_matrix, on the
+ * robust accumulator and moments; cost_out and grad_out of the two are
+ * bit-identical at the same x and cloud layout; the auto regroup is queued
+ * after the robust launch. fsdf_descend and fsdf_descend_lm inherit it through
+ * their host loops, and fsdf_set_lm_prior applies unchanged. The device loops
+ * do not serve a loss: fsdf_set_solver 1 / 3 and fsdf_set_lm_solver 1 take the
+ * host loop, the required modes (fsdf_set_solver 2 / 4, fsdf_set_lm_solver 2)
+ * return FSDF_ERR_STATE. fsdf_eval, fsdf_eval_device, fsdf_eval_moments,
+ * fsdf_eval_skin_moments, fsdf_skin, fsdf_raycast, fsdf_eval_state_device and
+ * fsdf_state_gradient are least squares always, whatever the loss. With
+ * FSDF_LOSS_SQUARE every call returns the bits it returned before there was a
+ * loss. */
+enum { FSDF_LOSS_SQUARE = 0, FSDF_LOSS_HUBER = 1, FSDF_LOSS_TUKEY = 2 };
+int fsdf_set_loss(fsdf_ctx* ctx, int32_t kind, double scale);
+/* fsdf_set_loss with the scale read through a pointer, for bindings that pass
+ * every floating-point argument by reference (julia/FlashSDF.jl); NULL reads
+ * as 0.0 (FSDF_LOSS_SQUARE ignores it). */
+int fsdf_set_loss_ref(fsdf_ctx* ctx, int32_t kind, const double* scale);
+int fsdf_get_loss(const fsdf_ctx* ctx, int32_t* kind_out, double* scale_out);
+int fsdf_eval_robust(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out /* [1+6S] */,
+                     double* moments_out /* [S][21] or NULL */, double* weight_out /* [S] or NULL */);
+
 /* ---- Gauss-Newton for RBF skins: device side -----------------------------------
  * The skins' second moments M_r above, reduced on the device
  * (csrc/skin_moments.hip): a launch of its own after the pass — the pass

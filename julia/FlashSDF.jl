@@ -248,14 +248,56 @@ type GPUCost{P} <: Function
     memo_accum::Vector{Float64}
     weight::Float64
     fresh::Bool   # the resident cloud has not been evaluated yet (the regroup follows its first pass)
+    robust::Bool  # a loss other than LOSS_SQUARE is set: the pass is fsdf_eval_robust's
 end
 
+# fsdf_set_loss kinds (include/flashsdf.h "robust point losses")
+const LOSS_SQUARE = Int32(0)
+const LOSS_HUBER = Int32(1)
+const LOSS_TUKEY = Int32(2)
+
+"""
+The robust point loss of the context (fsdf_set_loss): `kind` LOSS_HUBER or LOSS_TUKEY with a
+finite `scale` > 0, or LOSS_SQUARE (least squares, the default). Kept over model and cloud swaps.
+"""
+set_loss!(ctx::Context, kind::Integer, scale::Real) =   # (fsdf_set_loss with the scale by reference)
+    check(ctx.ptr, ccall((:fsdf_set_loss_ref, lib), Cint, (Ptr{Void}, Int32, Ptr{Float64}),
+                         ctx.ptr, Int32(kind), Float64[scale]), "set_loss")
+
+"(kind, scale) as the library holds them (fsdf_get_loss)."
+function get_loss(ctx::Context)
+    kind = Ref{Int32}(0); scale = Ref{Float64}(0)
+    check(ctx.ptr, ccall((:fsdf_get_loss, lib), Cint, (Ptr{Void}, Ref{Int32}, Ref{Float64}),
+                         ctx.ptr, kind, scale), "get_loss")
+    kind[], scale[]
+end
+
+"""
+One residual pass over the resident cloud of a hull-only scene and the per-surface sums of the
+context's loss, reduced on the device (fsdf_eval_robust): returns (cost Σρ, accumulator with the
+robust wrenches Σ 2 w d* v in fsdf_eval's layout, moments 21 x S of Σ w v vᵀ, weights Σ w per surface).
+"""
+function eval_robust(ctx::Context, poses::Vector{Float64})
+    S = div(length(poses), 12)
+    accum = zeros(1 + 6S)
+    moments = zeros(21, S)
+    weights = zeros(S)
+    c = Ref{Float64}(0)
+    check(ctx.ptr, ccall((:fsdf_eval_robust, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.ptr, poses, c, accum, moments, weights), "eval_robust")
+    c[], accum, moments, weights
+end
+
+"`loss = (kind, scale)`: a robust point loss in place of the squared distance (hull-only scenes)."
 function GPUCost(manipulator::Manipulator, sensed_points::AbstractVector;
-                 device::Integer=0, deformation_cost_weight=default_deformation_cost_weight)
+                 device::Integer=0, deformation_cost_weight=default_deformation_cost_weight,
+                 loss::Tuple=(LOSS_SQUARE, 0.0))
     ctx = Context(manipulator; device=device)
     set_points!(ctx, sensed_points)
+    set_loss!(ctx, loss[1], loss[2])
     GPUCost(manipulator, ctx, Dict{DataType, ManipulatorState}(), Float64[], Float64[],
-            Float64(deformation_cost_weight), true)
+            Float64(deformation_cost_weight), true, loss[1] != LOSS_SQUARE)
 end
 
 function state_for{T}(f::GPUCost, ::Type{T})
@@ -264,7 +306,7 @@ function state_for{T}(f::GPUCost, ::Type{T})
     end
 end
 
-"One residual pass per distinct value(x): cost Σ d² and the accumulator."
+"One residual pass per distinct value(x): cost Σ d² (with a loss: Σ ρ(d)) and the accumulator."
 function residual_pass!(f::GPUCost, geo::SceneGeometry, xv::Vector{Float64})
     if xv != f.memo_x
         poses, rows = device_inputs(geo)
@@ -274,10 +316,16 @@ function residual_pass!(f::GPUCost, geo::SceneGeometry, xv::Vector{Float64})
         end
         accum = zeros(f.ctx.accum_len)   # 1 + 6S + Σ(4n+4) (fsdf_accum_len)
         c = Ref{Float64}(0)
-        check(f.ctx.ptr, ccall((:fsdf_eval, lib), Cint,
-                               (Ptr{Void}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64},
-                                Ptr{Float64}),
-                               f.ctx.ptr, poses, c, accum, C_NULL, C_NULL, C_NULL), "eval")
+        if f.robust   # Σρ and the robust wrenches, in the same accumulator layout (hull-only scenes)
+            check(f.ctx.ptr, ccall((:fsdf_eval_robust, lib), Cint,
+                                   (Ptr{Void}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                   f.ctx.ptr, poses, c, accum, C_NULL, C_NULL), "eval_robust")
+        else
+            check(f.ctx.ptr, ccall((:fsdf_eval, lib), Cint,
+                                   (Ptr{Void}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64},
+                                    Ptr{Float64}),
+                                   f.ctx.ptr, poses, c, accum, C_NULL, C_NULL, C_NULL), "eval")
+        end
         if f.fresh   # once per frame, after its first pass (per-point results unchanged, sums to rounding)
             regroup_auto!(f.ctx)
             f.fresh = false

@@ -167,6 +167,14 @@ struct fsdf_ctx {
   fsdf::PinnedBuf<double> h_skin_moments;
   std::vector<fsdf::Event> skin_ev;  // skin-moments timing (fsdf_profile_pass): pairs around its launches
   size_t skin_ev_used = 0;
+  // robust point loss (fsdf_set_loss: a context setting, kept over model and cloud swaps) and the
+  // buffers of its reduction (fsdf_eval_robust and the iteration entry points with a loss;
+  // robust.hip): the workgroups' partials, the [S][29] (or [S][8]) rows, their pinned read-back
+  int loss_kind = FSDF_LOSS_SQUARE;
+  double loss_scale = 0.0;
+  fsdf::DevBuf<double> robust_partials, robust_rows;
+  fsdf::PinnedBuf<double> h_robust;
+  std::vector<double> robust_accum, robust_moments;  // the accumulator [1 + 6S] and moments [S][21] from the rows
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;
@@ -252,6 +260,12 @@ int ensure_host_acc(fsdf_ctx* c, int len);
 // (h_skin_moments) of any scene, kMomentsSkins the skins' alone)
 enum { kMomentsRigid = 0, kMomentsAll = 1, kMomentsSkins = 2 };
 int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who, int what = kMomentsRigid);
+// (the pass with k*, d*, ∇d* in resident order, then the robust launch: the rows [S][29] (moments)
+// or [S][8] to h_robust, in flight; hull-only scenes. robust_rows_finish, after the
+// synchronisation: robust_accum (fsdf_eval's layout, Σρ summed in surface order) and — moments —
+// robust_moments from the rows)
+int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool moments);
+void robust_rows_finish(fsdf_ctx* c, bool moments);
 int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
           double* grad_out, bool want_pp);
 // iterate.hip (the solver loops of descend.hip run on them)

@@ -295,8 +295,15 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
     declared = declared && D.n > 0;
     for (int j = 0; j < D.n; ++j) declared = declared && D.drow[j] < Mc.n_deform;
   }
+  // A loss other than SQUARE (fsdf_set_loss) is served by the host loop alone
+  // (the device step reads the pass's least-squares accumulator).
+  const bool loss = c->loss_kind != FSDF_LOSS_SQUARE;
+  if (loss && required && iteration_limit > 0)
+    return fail(c, FSDF_ERR_STATE,
+                "descend: the device loop was required (fsdf_set_solver %d) but a loss is set (fsdf_set_loss kind %d: "
+                "the host loop serves it)", c->solver_device, c->loss_kind);
   bool device_loop = c->solver_device && iteration_limit > 0 && (rigid || (c->solver_device >= 3 && declared)) &&
-                     c->n > 0;
+                     c->n > 0 && !loss;
   if (device_loop && !c->solver_tree_ok) {
     HIPCHECK(c, hipSetDevice(c->device));
     const int rc = build_solver_tree(c);
@@ -544,7 +551,12 @@ extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, 
   // the device loop (fsdf_set_lm_solver 1 / 2): a finite damping > 0 (the
   // step's raises of a degenerate factorisation are then bounded), resident
   // points, the moments table and both solver kernels' carves within their LDS
-  if (rigid && c->lm_solver_device && iteration_limit > 0) {
+  // A loss other than SQUARE (fsdf_set_loss): the host loop alone (mode 1 takes it, mode 2 is refused).
+  const bool loss = c->loss_kind != FSDF_LOSS_SQUARE;
+  if (loss && c->lm_solver_device == 2)
+    return fail(c, FSDF_ERR_STATE, "descend_lm: the device loop was required (fsdf_set_lm_solver 2) but a loss is set "
+                                   "(fsdf_set_loss kind %d: the host loop serves it)", c->loss_kind);
+  if (rigid && c->lm_solver_device && iteration_limit > 0 && !loss) {
     const bool required = c->lm_solver_device == 2;
     if (required && !(damping > 0.0))
       return fail(c, FSDF_ERR_ARG, "descend_lm: the device loop needs a damping > 0");

@@ -266,6 +266,36 @@ size_t moments_partials_len(int64_t n, int S);
 hipError_t launch_moments(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_grad, int64_t n,
                           int S, double* d_partials, double* d_moments, hipStream_t s, const int* skip = nullptr);
 
+// ---- robust point losses (robust.hip; the loss: robust_impl.h) -------------------
+// Per surface k one row of kRobustLen doubles over the resident points with
+// k* = k, w = w(d*), v = (∇d*, p × ∇d*): [0..20] Σ w v vᵀ (the moments' order),
+// [21..26] Σ 2 w d* v (the accumulator's wrench), [27] Σ ρ(d*), [28] Σ w. From
+// the per-point k*, d*, ∇d* a pass wrote in RESIDENT order. The grid, the runs
+// and the reduce are the moments': run = robust_run(n) chunks per workgroup
+// (at least kRobustMinChunks, at most kRobustMaxGroups workgroups: a function
+// of n alone), robust_waves(S) waves per workgroup, as many of 4, 2, 1 as have
+// room for their [S][29] tables in kRobustMaxLds (4 up to 70 surfaces, 2 up to
+// 141, 1 up to 282). moments = false keeps the last kRobustTail entries of
+// every row alone (rows of 8: wrench, Σρ, Σw), summed in the same order.
+constexpr int kRobustLen = 29;           // entries per surface
+constexpr int kRobustTail = 8;           // ... of which the wrench, Σρ and Σw
+constexpr int kRobustBlock = 256;        // 4 waves at most
+constexpr int kRobustMinChunks = 8;      // a workgroup's run of 64-point chunks, at least (a multiple of 4)
+constexpr int kRobustMaxGroups = 512;    // workgroups, at most
+constexpr int kRobustMaxLds = 65536;     // the workgroup's tables
+int robust_waves(int S);  // 0: not even one table fits
+int64_t robust_run(int64_t n);
+int robust_groups(int64_t n);
+bool robust_fit(int S);
+// doubles of d_partials for a cloud of n points (>= one workgroup's; sized for the rows of 29)
+size_t robust_partials_len(int64_t n, int S);
+// n > 0, robust_fit(S), a valid loss (kind, scale: robust_impl.h). d_pts: the
+// resident cloud (precision 64 / 32; all arithmetic fp64); d_rows [S][29]
+// (moments) or [S][8]. A k* outside [0, S) contributes nothing.
+hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
+                         const double* d_grad, int64_t n, int S, int kind, double scale, double* d_partials,
+                         double* d_rows, hipStream_t s);
+
 // ---- second moments of RBF skins (skin_moments.hip) ----------------------------
 // Per skin r of n centres, m = 4n + 4: M_r [m][m] = Σ_{p: k*(p) = r's surface}
 // j(p) j(p)ᵀ, j the point's row in the layout of the skin's accumulator block

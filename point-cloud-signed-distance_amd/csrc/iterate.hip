@@ -255,10 +255,49 @@ double g_host_t[8];  // (ctx.h: the host loop's clocks, printed by fsdf_descend)
 long g_host_n;
 #endif
 
+// With a loss other than SQUARE set (fsdf_set_loss): the same iteration on the
+// robust objective Σρ(d*) — the pass with k*, d*, ∇d* in resident order, the
+// robust launch (robust.hip) in place of the pass's own sums, and the same
+// chain rule on the accumulator assembled from its rows. The auto regroup is
+// queued after the robust launch: it reads the layout the pass ran on. Rigid
+// scenes only. hess_out null: the rows without the moments (the same (c, g) bits).
+static int robust_iteration(fsdf_ctx* c, const double* x, double* cost_out, double* grad_out, double* hess_out,
+                            const char* who) {
+  if (c->lm.R > 0 || c->mech.n_deform > 0)
+    return fail(c, FSDF_ERR_STATE,
+                "%s: the loss set by fsdf_set_loss (kind %d) serves rigid scenes (no RBF skin, no deformation)", who,
+                c->loss_kind);
+  int rc = iteration_prepare(c, x, who);
+  if (rc) return rc;
+  auto& M = c->mech;
+  const bool moments = hess_out != nullptr;
+  rc = run_pass_robust(c, M.poses.data(), who, moments);
+  if (rc) return rc;
+  rc = iteration_regroup(c);  // (stream-ordered after the pass and the robust launch: the sync below covers it)
+  if (rc) return rc;
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  robust_rows_finish(c, moments);
+  rc = iteration_finish(c, x, c->robust_accum.data(), cost_out, grad_out, who);
+  if (rc || !moments) return rc;
+  const int nq = M.nq;
+  M.gn_work.resize((size_t)36 * M.nb + (size_t)6 * nq);
+  rc = fsdf_gauss_newton_matrix(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.Rb.data(),
+                                M.tb.data(), x, c->lm.S, M.surface_body.data(), c->robust_moments.data(), nq,
+                                M.gn_work.data(), hess_out);
+  if (rc) return fail(c, rc, "%s: Gauss-Newton matrix", who);
+  for (size_t i = 0; i < (size_t)nq * nq; ++i) hess_out[i] = 2.0 * hess_out[i];
+  return FSDF_OK;
+}
+
+static int robust_value_and_gradient(fsdf_ctx* c, const double* x, double* cost_out, double* grad_out) {
+  return robust_iteration(c, x, cost_out, grad_out, nullptr, "value_and_gradient");
+}
+
 extern "C" int fsdf_value_and_gradient(fsdf_ctx* c, const double* x, double* cost_out, double* grad_out) {
   if (!c) return FSDF_ERR_ARG;
   HOST_STAMP(0);
   if (!x || !cost_out || !grad_out) return fail(c, FSDF_ERR_ARG, "value_and_gradient: null argument");
+  if (c->loss_kind != FSDF_LOSS_SQUARE) return robust_value_and_gradient(c, x, cost_out, grad_out);
   int rc = iteration_prepare(c, x, "value_and_gradient");
   if (rc) return rc;
   auto& M = c->mech;
@@ -300,6 +339,8 @@ extern "C" int fsdf_value_gradient_hessian(fsdf_ctx* c, const double* x, double*
   if (!c) return FSDF_ERR_ARG;
   if (!x || !cost_out || !grad_out || !hess_out)
     return fail(c, FSDF_ERR_ARG, "value_gradient_hessian: null argument");
+  if (c->loss_kind != FSDF_LOSS_SQUARE)
+    return robust_iteration(c, x, cost_out, grad_out, hess_out, "value_gradient_hessian");
   const bool rigid = c->lm.R == 0 && c->mech.n_deform == 0;
   if (!rigid && !c->lm_skins)
     return fail(c, FSDF_ERR_STATE,

@@ -2,7 +2,8 @@
 // partial sums, the pose ring, the planned pass and its plan, the per-point
 // outputs and their read-back, fsdf_eval / fsdf_eval_device, the permutation
 // getters, and the pass followed by the second-moments reduction
-// (run_pass_moments, fsdf_eval_moments).
+// (run_pass_moments, fsdf_eval_moments) or by the sums of a robust point loss
+// (fsdf_set_loss, run_pass_robust, fsdf_eval_robust).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "robust_impl.h"
 
 // default plan composition: chunks split over 4 / 2 waves (fsdf_set_plan shares < 0)
 static constexpr int64_t kPlanDefault4 = 96, kPlanDefault2 = 192;
@@ -474,5 +476,119 @@ extern "C" int fsdf_skin_moments_time(fsdf_ctx* c, double* total_ms, int64_t* la
   *total_ms = t;
   *launches = (int64_t)(c->skin_ev_used / 2);
   c->skin_ev_used = 0;
+  return FSDF_OK;
+}
+
+// ---- robust point losses (robust.hip, robust_impl.h) ---------------------------------
+extern "C" int fsdf_set_loss(fsdf_ctx* c, int32_t kind, double scale) {
+  if (!c) return FSDF_ERR_ARG;
+  if (kind != FSDF_LOSS_SQUARE && kind != FSDF_LOSS_HUBER && kind != FSDF_LOSS_TUKEY)
+    return fail(c, FSDF_ERR_ARG, "set_loss: unknown kind %d", kind);
+  if (!fsdf::robust::valid(kind, scale))
+    return fail(c, FSDF_ERR_ARG, "set_loss: the scale of a Huber or Tukey loss must be finite and > 0 (got %g)", scale);
+  c->loss_kind = kind;
+  c->loss_scale = kind == FSDF_LOSS_SQUARE ? 0.0 : scale;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_loss_ref(fsdf_ctx* c, int32_t kind, const double* scale) {
+  return fsdf_set_loss(c, kind, scale ? *scale : 0.0);
+}
+
+extern "C" int fsdf_get_loss(const fsdf_ctx* c, int32_t* kind_out, double* scale_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (kind_out) *kind_out = c->loss_kind;
+  if (scale_out) *scale_out = c->loss_scale;
+  return FSDF_OK;
+}
+
+// One pass over the resident cloud and the per-surface sums of the context's
+// loss (robust.hip), for fsdf_eval_robust and the iteration entry points with
+// a loss set: the rows go to c->h_robust, in flight on the context stream when
+// this returns — the caller synchronises (and regroups, if it does, after
+// this: the launch reads the layout the pass ran on), then robust_rows_finish.
+// The order is run_pass_moments': (1) reserve every buffer the per-point
+// outputs and the rows touch; (2) read their pointers into locals; (3) launch
+// with the locals. A cloud of no points launches no robust kernel: zero rows.
+// The pass's own least-squares accumulator goes to the context's device
+// accumulator and is not read.
+int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool moments) {
+  const int S = c->lm.S;
+  if (c->lm.R > 0 || c->mech.n_deform > 0)
+    return fail(c, FSDF_ERR_STATE, "%s: a robust loss serves hull-only scenes (no RBF skin, no deformation)", who);
+  if (!fsdf::robust_fit(S))
+    return fail(c, FSDF_ERR_STATE,
+                "%s: the robust table of %d surfaces (%zu bytes) does not fit %d bytes of LDS (at most 282 surfaces)",
+                who, S, (size_t)S * fsdf::kRobustLen * sizeof(double), fsdf::kRobustMaxLds);
+  const int64_t n = c->n;
+  const size_t rlen = (size_t)S * (moments ? fsdf::kRobustLen : fsdf::kRobustTail);
+  // (1) reserve
+  int rc = ensure_outputs(c, n);
+  if (rc) return rc;
+  HIPCHECK(c, c->robust_partials.reserve(fsdf::robust_partials_len(n, S)));
+  HIPCHECK(c, c->robust_rows.reserve((size_t)S * fsdf::kRobustLen));
+  HIPCHECK(c, c->h_robust.reserve((size_t)S * fsdf::kRobustLen));
+  // (2) read the pointers
+  const void* d_pts = c->cur.pts.get();
+  int32_t* d_kstar = c->kstar.get();
+  double* d_d = c->d.get();
+  double* d_grad = c->grad.get();
+  double* d_partials = c->robust_partials.get();
+  double* d_rows = c->robust_rows.get();
+  double* h_rows = c->h_robust.get();
+  double* d_accum = c->model.accum.get();
+  // (3) launch: the pass with k*, d* and ∇d* in resident order (no permutation), the robust sums, their read-back
+  rc = run_pass(c, poses, d_pts, n, d_accum, d_kstar, d_d, d_grad, nullptr, true);
+  if (rc) return rc;
+  if (n == 0) {
+    HIPCHECK(c, hipStreamSynchronize(c->stream));  // (an earlier read-back into the rows)
+    memset(h_rows, 0, rlen * sizeof(double));
+    return FSDF_OK;
+  }
+  HIPCHECK(c, fsdf::launch_robust(c->precision, moments, d_pts, d_kstar, d_d, d_grad, n, S, c->loss_kind,
+                                  c->loss_scale, d_partials, d_rows, c->stream));
+  HIPCHECK(c, hipMemcpyAsync(h_rows, d_rows, rlen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  return FSDF_OK;
+}
+
+// the accumulator in fsdf_eval's layout (Σρ summed in surface order from 0.0, then every surface's
+// wrench) and — moments — the [S][21] moments, from the rows read back
+void robust_rows_finish(fsdf_ctx* c, bool moments) {
+  const int S = c->lm.S, len = moments ? fsdf::kRobustLen : fsdf::kRobustTail, m0 = len - fsdf::kRobustTail;
+  const double* rows = c->h_robust.get();
+  c->robust_accum.assign((size_t)1 + 6 * (size_t)S, 0.0);
+  double cost = 0.0;
+  for (int k = 0; k < S; ++k) {
+    const double* r = rows + (size_t)len * k;
+    cost += r[m0 + 6];
+    for (int i = 0; i < 6; ++i) c->robust_accum[(size_t)1 + 6 * (size_t)k + i] = r[m0 + i];
+  }
+  c->robust_accum[0] = cost;
+  if (moments) {
+    c->robust_moments.resize((size_t)S * fsdf::kMomentsLen);
+    for (int k = 0; k < S; ++k)
+      memcpy(c->robust_moments.data() + (size_t)fsdf::kMomentsLen * k, rows + (size_t)len * k,
+             fsdf::kMomentsLen * sizeof(double));
+  }
+}
+
+extern "C" int fsdf_eval_robust(fsdf_ctx* c, const double* poses, double* cost_out, double* accum_out,
+                                double* moments_out, double* weight_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval_robust: no model (call fsdf_set_model first)");
+  if (!poses) return fail(c, FSDF_ERR_ARG, "eval_robust: poses required");
+  HIPCHECK(c, hipSetDevice(c->device));
+  if (c->lm.R > 0) return fail(c, FSDF_ERR_STATE, "eval_robust: hull-only scenes (the scene has an RBF skin)");
+  const bool moments = moments_out != nullptr;
+  const int rc = run_pass_robust(c, poses, "eval_robust", moments);
+  if (rc) return rc;
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  robust_rows_finish(c, moments);
+  const int S = c->lm.S, len = moments ? fsdf::kRobustLen : fsdf::kRobustTail;
+  if (cost_out) *cost_out = c->robust_accum[0];
+  if (accum_out) memcpy(accum_out, c->robust_accum.data(), c->robust_accum.size() * sizeof(double));
+  if (moments) memcpy(moments_out, c->robust_moments.data(), c->robust_moments.size() * sizeof(double));
+  if (weight_out)
+    for (int k = 0; k < S; ++k) weight_out[k] = c->h_robust.get()[(size_t)len * k + len - 1];
   return FSDF_OK;
 }

@@ -1,0 +1,184 @@
+// robust.hip — the per-surface sums of a robust point loss on the device
+// (include/flashsdf.h "robust point losses"; the loss itself: robust_impl.h).
+// Per surface k over the resident points with k*(p) = k, with w = w(d*),
+// v = (∇d*, p × ∇d*): the IRLS moments Σ w v vᵀ (21 entries), the wrench
+// Σ 2 w d* v (6), Σ ρ(d*) and Σ w — one row of kRobustLen = 29 doubles
+// (MOMENTS = false: the last 8 alone, for callers that need no Hessian). From
+// the per-point k*, d* and ∇d* a pass wrote in resident order: a launch of its
+// own after the pass (the pass kernels are not touched), then the pass's tile
+// reduce over the workgroups' partials.
+//
+// The design is moments_kernel's (moments.hip): every workgroup owns a fixed,
+// contiguous run of 64-point chunks (robust_run: a function of n alone), each of
+// its waves a contiguous share of the run and an [S][len] fp64 table of its own
+// in LDS — as many waves (4, 2 or 1) as have room for their [S][29] tables
+// (robust_waves: a function of S alone, the same for both variants, so their
+// common entries are summed in the same order: the same bits). Lanes carry
+// their sums from chunk to chunk while their k* stays the same; when a lane's
+// k* changes (and at the end) a ballot loop over the wave's distinct k* sums
+// each entry with a masked DPP wave sum, entry e ending in lane e, and lanes
+// 0..len-1 add them to row k of the wave's table (consecutive doubles: no bank
+// conflict). The waves' tables are summed in wave order into the workgroup's
+// partial. No floating-point atomics: the summation order is a function of
+// (n, S, the resident order, k*) alone, so results are bit-identical from run
+// to run.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "fsdf_internal.h"
+#include "robust_impl.h"
+#include "sdf_device_math.h"
+
+namespace fsdf {
+
+static_assert(kRobustMinChunks % (kRobustBlock / 64) == 0, "a run is whole rounds of one chunk per wave");
+static_assert(kRobustLen == kMomentsLen + kRobustTail, "a row: the moments, then the wrench, the cost and the weight");
+
+int64_t robust_run(int64_t n) {
+  const int64_t nc = (n + 63) / 64, waves = kRobustBlock / 64;
+  const int64_t run = std::max<int64_t>(kRobustMinChunks, (nc + kRobustMaxGroups - 1) / kRobustMaxGroups);
+  return (run + waves - 1) / waves * waves;
+}
+
+int robust_groups(int64_t n) {
+  const int64_t nc = (n + 63) / 64, run = robust_run(n);
+  return (int)((nc + run - 1) / run);
+}
+
+int robust_waves(int S) {
+  const size_t table = (size_t)std::max(S, 1) * kRobustLen * sizeof(double);
+  for (int w = kRobustBlock / 64; w >= 1; w /= 2)
+    if (w * table <= (size_t)kRobustMaxLds) return w;
+  return 0;
+}
+
+bool robust_fit(int S) { return S >= 1 && robust_waves(S) >= 1; }
+
+size_t robust_partials_len(int64_t n, int S) {
+  // (whole 8-entry line tiles: reduce_tiles_kernel's layout)
+  return (size_t)((kRobustLen * S + 7) & ~7) * (size_t)std::max(robust_groups(n), 1);
+}
+
+extern __shared__ __attribute__((aligned(16))) double robust_tab[];  // [waves][S][LEN]
+
+// blockDim.x / 64 waves; run is a multiple of them
+template <typename T, bool MOMENTS>
+__global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restrict__ pts,
+                                                              const int32_t* __restrict__ kstar,
+                                                              const double* __restrict__ dstar,
+                                                              const double* __restrict__ grad, int64_t n, int S,
+                                                              int run, int kind, double scale,
+                                                              double* __restrict__ partials) {
+  constexpr int LEN = MOMENTS ? kRobustLen : kRobustTail;
+  constexpr int M0 = LEN - kRobustTail;  // the wrench's first entry; Σρ at M0 + 6, Σw at M0 + 7
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+  const int len = LEN * S;
+  for (int t = tid; t < waves * len; t += blockDim.x) robust_tab[t] = 0.0;
+  __syncthreads();
+  double* tab = robust_tab + wave * len;  // this wave's own
+  const int share = run / waves;
+  const int64_t c0 = (int64_t)blockIdx.x * run + (int64_t)wave * share;
+  // each lane's sums over its own points while its k* stays the same (ck: the
+  // surface they belong to, -1: none yet), as moments_kernel's
+  int ck = -1;
+  double acc[LEN];
+#pragma unroll
+  for (int e = 0; e < LEN; ++e) acc[e] = 0.0;
+  // the carried sums into the table: per distinct surface of the wave (that of
+  // its first lane still to be summed) a masked wave sum of each entry, entry e
+  // ending in lane e (rem is wave-uniform: the sums run with the whole wave active)
+  auto flush = [&]() {
+    unsigned long long rem = __ballot(ck >= 0);
+    while (rem != 0) {
+      const int kk = __builtin_amdgcn_readlane(ck, __ffsll((long long)rem) - 1);
+      const bool in = ck == kk;
+      rem &= ~__ballot(in);
+      double mine = 0.0;
+#pragma unroll
+      for (int e = 0; e < LEN; ++e) {
+        const double s = wave_sum(in ? acc[e] : 0.0);
+        mine = lane == e ? s : mine;
+      }
+      if (lane < LEN) tab[LEN * kk + lane] += mine;
+    }
+    ck = -1;
+#pragma unroll
+    for (int e = 0; e < LEN; ++e) acc[e] = 0.0;
+  };
+  for (int r = 0; r < share; ++r) {
+    // a lane beyond n, or whose k* is not a surface of the scene, contributes nothing
+    const int64_t i = (c0 + r) * 64 + lane;
+    int k = -1;
+    if (i < n) {
+      k = kstar[i];
+      if (k < 0 || k >= S) k = -1;
+    }
+    if (__ballot(k >= 0 && ck >= 0 && k != ck) != 0) flush();
+    if (k >= 0) {
+      const double px = (double)pts[3 * i], py = (double)pts[3 * i + 1], pz = (double)pts[3 * i + 2];
+      const double d = dstar[i];
+      double v[6];
+      v[0] = grad[3 * i];
+      v[1] = grad[3 * i + 1];
+      v[2] = grad[3 * i + 2];
+      v[3] = py * v[2] - pz * v[1];
+      v[4] = pz * v[0] - px * v[2];
+      v[5] = px * v[1] - py * v[0];
+      const double w = robust::weight(kind, scale, d);
+      if (MOMENTS) {
+        int e = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+          const double wa = w * v[a];
+#pragma unroll
+          for (int b = a; b < 6; ++b, ++e) acc[e] += wa * v[b];
+        }
+      }
+      const double t = robust::wrench_scale(w, d);
+#pragma unroll
+      for (int a = 0; a < 6; ++a) acc[M0 + a] += t * v[a];
+      acc[M0 + 6] += robust::rho(kind, scale, d);
+      acc[M0 + 7] += w;
+      ck = k;
+    }
+  }
+  flush();
+  __syncthreads();
+  // the waves' tables in wave order: this workgroup's partial, in the line tiles
+  // reduce_tiles_kernel reads (pass_kernels.h pidx: entry t of block b at [t / 8][b][t % 8])
+  for (int t = tid; t < len; t += blockDim.x) {
+    double s = robust_tab[t];
+    for (int w = 1; w < waves; ++w) s += robust_tab[w * len + t];
+    partials[((int64_t)(t >> 3) * gridDim.x + blockIdx.x) * 8 + (t & 7)] = s;
+  }
+}
+
+hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
+                         const double* d_grad, int64_t n, int S, int kind, double scale, double* d_partials,
+                         double* d_rows, hipStream_t s) {
+  if (n <= 0 || !robust_fit(S) || !robust::valid(kind, scale) || !d_pts || !d_kstar || !d_d || !d_grad ||
+      !d_partials || !d_rows)
+    return hipErrorInvalidValue;
+  const int groups = robust_groups(n), run = (int)robust_run(n), waves = robust_waves(S), block = 64 * waves;
+  const int len = moments ? kRobustLen : kRobustTail;
+  const size_t lds = (size_t)waves * S * len * sizeof(double);
+#define FSDF_ROBUST_LAUNCH(T, M)                                                                              \
+  hipLaunchKernelGGL((robust_kernel<T, M>), dim3(groups), dim3(block), lds, s, (const T*)d_pts, d_kstar, d_d, \
+                     d_grad, n, S, run, kind, scale, d_partials)
+  if (precision == 64) {
+    if (moments) FSDF_ROBUST_LAUNCH(double, true);
+    else FSDF_ROBUST_LAUNCH(double, false);
+  } else {
+    if (moments) FSDF_ROBUST_LAUNCH(float, true);
+    else FSDF_ROBUST_LAUNCH(float, false);
+  }
+#undef FSDF_ROBUST_LAUNCH
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // the partials in workgroup order (the pass's tile reduce: fixed order)
+  return launch_reduce(d_partials, groups, len * S, d_rows, s);
+}
+
+}  // namespace fsdf

@@ -10,11 +10,12 @@ from .core import (BodyGeometry, ConvexGeometry, DeformableInterpolatingSkin, In
                    num_deformations, num_states, skin, surfaces)
 from . import models as Models  # noqa: N812
 from ._lib import FlashNativeError
+from .robust import Huber, Tukey
 
 __all__ = ["BodyGeometry", "ConvexGeometry", "DeformableInterpolatingSkin", "InterpolatingGeometry",
            "Manipulator", "ManipulatorState", "RigidInterpolatingSkin", "SceneSkin", "hull_poses",
            "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError",
-           "LevenbergMarquardt"]
+           "LevenbergMarquardt", "Huber", "Tukey"]
 
 
 def __getattr__(name):

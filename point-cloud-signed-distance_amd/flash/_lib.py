@@ -121,6 +121,10 @@ _PROTOS = {
     "fsdf_set_lm_skins": (c_int32, [c_void_p, c_int32]),
     "fsdf_skin_moments_time": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
     "fsdf_eval_skin_moments": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
+    "fsdf_set_loss": (c_int32, [c_void_p, c_int32, c_double]),
+    "fsdf_set_loss_ref": (c_int32, [c_void_p, c_int32, POINTER(c_double)]),
+    "fsdf_get_loss": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_double)]),
+    "fsdf_eval_robust": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p, c_void_p]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -444,6 +448,42 @@ class Context:
         check(self._lib.fsdf_eval_moments(self._ctx, ptr(p), ctypes.byref(cost), ptr(accum), ptr(mom)), self._ctx,
               "eval_moments")
         return cost.value, accum, mom
+
+    def set_loss(self, loss):
+        """fsdf_set_loss: the robust point loss of value_and_gradient,
+        value_gradient_hessian, descend, descend_lm and eval_robust — a
+        flash.robust.Huber / Tukey (anything with .kind and .scale), or None
+        for least squares (the default). A context setting: model and cloud
+        swaps keep it."""
+        kind, scale = (0, 0.0) if loss is None else (int(loss.kind), float(loss.scale))
+        check(self._lib.fsdf_set_loss(self._ctx, kind, scale), self._ctx, "set_loss")
+        self._loss = loss
+
+    @property
+    def loss(self):
+        """The loss last given to set_loss (None: least squares); the library's
+        own record is (kind, scale) = loss_setting()."""
+        return getattr(self, "_loss", None)
+
+    def loss_setting(self):
+        """fsdf_get_loss: (kind, scale) as the library holds them."""
+        kind, scale = c_int32(0), c_double(0.0)
+        check(self._lib.fsdf_get_loss(self._ctx, ctypes.byref(kind), ctypes.byref(scale)), self._ctx, "get_loss")
+        return kind.value, scale.value
+
+    def eval_robust(self, poses, moments: bool = True):
+        """fsdf_eval_robust: one pass over the resident cloud and the
+        per-surface sums of the context's loss, reduced on the device ->
+        (cost = Σρ, accum [1 + 6K] with the robust wrenches, moments [K, 21] =
+        Σ w v vᵀ or None, weights [K] = Σ w). Hull-only scenes."""
+        p = self._poses(poses)
+        accum = np.empty(1 + 6 * self.K, np.float64)
+        mom = np.empty((self.K, 21), np.float64) if moments else None
+        wts = np.empty(self.K, np.float64)
+        cost = c_double(0.0)
+        check(self._lib.fsdf_eval_robust(self._ctx, ptr(p), ctypes.byref(cost), ptr(accum), ptr(mom), ptr(wts)),
+              self._ctx, "eval_robust")
+        return cost.value, accum, mom, wts
 
     def eval_skin_moments(self, poses):
         """fsdf_eval_skin_moments: one pass over the resident cloud and the

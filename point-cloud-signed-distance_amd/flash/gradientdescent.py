@@ -113,7 +113,7 @@ class CostFunctor:
     every evaluation); each call ships only the hull poses."""
 
     def __init__(self, manipulator: Manipulator, sensed_points, device: int = 0, precision: int = 64,
-                 deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False):
+                 deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False, loss=None):
         self.manipulator = manipulator
         self.sensed_points = np.ascontiguousarray(sensed_points, np.float64).reshape(-1, 3)
         self.weight = deformation_cost_weight
@@ -138,6 +138,27 @@ class CostFunctor:
         self.skin_hessian = False
         if skin_hessian:
             self.set_skin_hessian(True)
+        # loss: a robust point loss (flash.robust.Huber / Tukey; None: least
+        # squares) for __call__, value_and_gradient, value_gradient_hessian,
+        # descend and descend_lm (fsdf_set_loss; native rigid scenes)
+        self.loss = None
+        self.set_loss(loss)
+
+    def set_loss(self, loss):
+        """The robust point loss of this functor's objective (flash.robust;
+        None: least squares, the default): Σρ(d*) in place of Σd*², its
+        gradient, and the IRLS Gauss-Newton Hessian (fsdf_set_loss; reduced on
+        the device, csrc/robust.hip). Native rigid scenes only. per_point and
+        the least-squares queries of the context are not affected."""
+        if loss is not None and not (self._native and self.rigid):
+            raise NotImplementedError("loss: robust losses serve native rigid scenes (no RBF skin, no deformation)")
+        self.loss = loss
+        self._assert_loss()
+
+    def _assert_loss(self):
+        # (the engine is shared: another functor of it may have set its own)
+        if self.ctx.loss != self.loss:
+            self.ctx.set_loss(self.loss)
 
     def set_skin_hessian(self, enable: bool = True):
         """Turn the Gauss-Newton Hessian of non-rigid scenes on or off
@@ -196,15 +217,19 @@ class CostFunctor:
         return c + _regularizer(self.state, self.weight), accum, extras
 
     def __call__(self, x) -> float:
+        if self.loss is not None:  # (the robust objective: the native iteration's cost)
+            return self.value_and_gradient(x)[0]
         return self._pass(x)[0]
 
     def value_and_gradient(self, x):
-        """(c(x), ∂c/∂x) from one residual pass."""
+        """(c(x), ∂c/∂x) from one residual pass (with a loss: of the robust
+        objective Σρ(d*))."""
         x = np.asarray(x, np.float64)
         if self._native:
             self._ensure_resident()
             if getattr(self.ctx, "_mechanism_of", None) != (self.manipulator, self.weight):
                 self._register_native()  # another functor of this engine registered its own
+            self._assert_loss()
             return self.ctx.value_and_gradient(x)
         c, accum, _ = self._pass(x)
         return c, gradient_from_accum(self.manipulator, x, accum, self._solves, self.weight)
@@ -217,6 +242,7 @@ class CostFunctor:
         self._ensure_resident()
         if getattr(self.ctx, "_mechanism_of", None) != (self.manipulator, self.weight):
             self._register_native()
+        self._assert_loss()
         return self.ctx.descend(x, iteration_limit, rate, max_step, tolerance, divisors, n_points)
 
     def _native_rigid(self, who):
@@ -227,6 +253,7 @@ class CostFunctor:
             self._register_native()
         if getattr(self.ctx, "lm_skins", False) != self.skin_hessian:  # (another functor of this engine set its own)
             self.ctx.set_lm_skins(self.skin_hessian)
+        self._assert_loss()
 
     def value_gradient_hessian(self, x):
         """(c(x), ∂c/∂x, the Gauss-Newton Hessian 2 JᵀJ) from one residual pass

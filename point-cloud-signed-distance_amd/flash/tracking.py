@@ -137,7 +137,10 @@ class LevenbergMarquardt:
     skins (False): True admits native scenes with RBF skins and deformations in
     estimate_state / Tracker / track — the cost's skin_hessian is turned on
     (fsdf_set_lm_skins: the skins' second moments reduced on the device, H over
-    the whole state [q; δ]; the host loop). The default refuses them as before."""
+    the whole state [q; δ]; the host loop). The default refuses them as before.
+    With a robust point loss (estimate_state / Tracker / track `loss=`,
+    flash.robust) f is Σρ(d*)/N and H the IRLS Gauss-Newton Hessian; the loop
+    is the host loop whatever device_loop says ("require" is refused)."""
     num_vars: int
     damping: float = 1e-3
     max_step: float = 0.5
@@ -190,7 +193,7 @@ def _default_solver(manipulator):
     return NaiveSolver(num_states(manipulator), rate=0.1, max_step=0.5, iteration_limit=30)
 
 
-def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
+def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, loss=None):
     """wrapped_cost (src/tracking.jl:16-21) over a CostFunctor, then optimize!.
     Without a callback, a NaiveSolver runs natively (fsdf_descend: the same
     arithmetic, no Python round trip per iteration), and so does a
@@ -198,8 +201,15 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
     solver's prior_weight and device_loop); with a callback its Python loop
     runs over the objective wrapped in state_prior. A native scene with RBF
     skins or deformations is admitted only by LevenbergMarquardt(skins=True),
-    which turns the cost's skin_hessian on."""
+    which turns the cost's skin_hessian on.
+    loss (flash.robust.Huber / Tukey; None: the functor as it is): handed to
+    the functor (CostFunctor.set_loss) before anything runs, so every path
+    above — the native loops, the Python loops, the callback's cost — is over
+    the robust objective Σρ(d*)/N. The device-resident loops do not serve a
+    loss: device_loop=True runs the host loop, "require" is refused."""
     n = max(n_points, 1)
+    if loss is not None:
+        cost.set_loss(loss)
     if callback is None and type(solver) is NaiveSolver and cost._native:
         x0 = np.asarray(x_estimated, np.float64)
         div = solver.precondition_divisors
@@ -247,15 +257,17 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver):
 
 
 def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callback=None, solver=None,
-                   device: int = 0, precision: int = 64):
+                   device: int = 0, precision: int = 64, loss=None):
     """Tracking.estimate_state (src/tracking.jl:8-27). Returns the solution x.
 
     The default callback accepts (x, c): the reference's default `x -> ()` is
-    called with two arguments (src/tracking.jl:9 vs :19) and would throw."""
+    called with two arguments (src/tracking.jl:9 vs :19) and would throw.
+    loss: a robust point loss (flash.robust.Huber / Tukey) in place of the
+    squared distance — native rigid scenes; the callback then sees Σρ(d*)."""
     pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
     solver = solver or _default_solver(manipulator)
     cost = CostFunctor(manipulator, pts, device=device, precision=precision)
-    return _optimize(cost, len(pts), x_estimated, callback, solver)
+    return _optimize(cost, len(pts), x_estimated, callback, solver, loss=loss)
 
 
 def notebook_frame_solver(manipulator):
@@ -271,11 +283,12 @@ class Tracker:
     iteration are recorded (host FK + pass + chain rule, end to end)."""
 
     def __init__(self, manipulator: Manipulator, state: ManipulatorState | None = None, solver=None,
-                 device: int = 0, precision: int = 64):
+                 device: int = 0, precision: int = 64, loss=None):
         self.manipulator = manipulator
         self.state = state if state is not None else ManipulatorState(manipulator)
         self.solver = solver or notebook_frame_solver(manipulator)
         self.cost = CostFunctor(manipulator, np.zeros((0, 3)), device=device, precision=precision)
+        self.loss = loss  # a robust point loss for every frame (flash.robust; None: least squares)
         self.frame_ms: list[float] = []
         self.set_points_ms: list[float] = []
         self.iterations: list[int] = []
@@ -290,7 +303,7 @@ class Tracker:
         if next_points is not None:
             self.cost.prefetch_sensed_points(next_points)
         t1 = time.perf_counter()
-        x = _optimize(self.cost, len(pts), flatten(self.state), callback, self.solver)
+        x = _optimize(self.cost, len(pts), flatten(self.state), callback, self.solver, loss=self.loss)
         unflatten(self.state, x)
         t2 = time.perf_counter()
         self.set_points_ms.append((t1 - t0) * 1e3)
@@ -305,11 +318,12 @@ class Tracker:
 
 
 def track(manipulator: Manipulator, frames, state: ManipulatorState | None = None, solver=None, callback=None,
-          device: int = 0, precision: int = 64):
+          device: int = 0, precision: int = 64, loss=None):
     """for event in log: gradient_descent!(state, model, sensed_points)
     (examples/irb_and_squishable.ipynb cells 11-12). `frames` yields sensed
-    clouds ([n,3]); returns (the per-frame solutions [F, n_states], the Tracker)."""
-    tr = Tracker(manipulator, state, solver, device, precision)
+    clouds ([n,3]); returns (the per-frame solutions [F, n_states], the Tracker).
+    loss: a robust point loss for every frame (flash.robust)."""
+    tr = Tracker(manipulator, state, solver, device, precision, loss=loss)
     xs = []
     it = iter(frames)
     cur = next(it, None)

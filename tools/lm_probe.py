@@ -18,7 +18,10 @@ the device-resident loop (fsdf_set_lm_solver 2) instead of the host loop;
 --prior W gives them the prior of fsdf_set_lm_prior at a uniform weight W, or
 scaled per coordinate by the points of the joint's subtree (--prior-scale
 subtree: W · N / points nearest a surface of the subtree; f is then the wrapped
-objective's, the prior included).
+objective's, the prior included). --loss huber:0.02 | tukey:0.05 gives every
+frame (and, without --frames, every timed call) that robust point loss
+(fsdf_set_loss: f is then Σρ/N, the LM frames run the host loop); the table
+also carries the error over the three base joints of each arm.
 
 And for the kernels' own times a kernel trace of the Hessian calls alone
 (no counters in the same run):
@@ -52,7 +55,7 @@ def run(a):
         m = Models.arm_grid() if model == "m64" else Models.irb140()
         q_true, q = synthetic.perturbed_configuration(m, 1234)
         q = np.asarray(q, np.float64)
-        cf = CostFunctor(m, synthetic.depth_cloud(m, q_true, n, seed=1234 + 17))
+        cf = CostFunctor(m, synthetic.depth_cloud(m, q_true, n, seed=1234 + 17), loss=a.loss)
         for _ in range(5):  # the cloud's first pass, the regroup, the block order / plan, allocations
             cf.value_and_gradient(q)
             cf.value_gradient_hessian(q)
@@ -66,6 +69,7 @@ def run(a):
             cf.value_gradient_hessian(q)
             vgh.append((time.perf_counter() - t0) * 1e6)
         out = {"model": model, "points": n, "reps": a.reps, "pass_kernel": cf.ctx.pass_kernel_name(),
+               "loss": repr(a.loss) if a.loss is not None else None,
                "value_gradient_hessian_us": statistics.median(vgh),
                "value_gradient_hessian_us_p10_p90": [float(np.percentile(vgh, 10)), float(np.percentile(vgh, 90))]}
         if vg:
@@ -89,8 +93,10 @@ def frames(a):
         q_true, q = synthetic.perturbed_configuration(m, 1234)
         q = np.asarray(q, np.float64)
         pts = synthetic.depth_cloud(m, q_true, n, seed=1234 + 17)
-        cf = CostFunctor(m, pts)
+        cf = CostFunctor(m, pts, loss=a.loss)
         f_true = cf.value_and_gradient(np.asarray(q_true, np.float64))[0] / n
+        # the three base joints of each arm (IRB140: six revolute joints per arm, in arm order)
+        base = np.array([j for j in range(len(q)) if j % 6 < 3])
         solvers = [("naive", None)] + [("lm", k) for k in a.limits]
         if a.device_loop:  # (the default is the host loop: an A/B library from before the switch runs it too)
             cf.ctx.set_lm_solver("require")
@@ -115,7 +121,9 @@ def frames(a):
                        "frame_ms": statistics.median(ms[1:]), "evaluations": its, "f": f, "f_at_q_true": f_true,
                        "lm_loop": "device" if a.device_loop else "host", "prior": a.prior,
                        "prior_scale": a.prior_scale if a.prior is not None else None,
-                       "max_abs_q_error": float(np.abs(x - q_true).max())}
+                       "max_abs_q_error": float(np.abs(x - q_true).max()),
+                       "max_abs_base_joint_error": float(np.abs(x - q_true)[base].max()),
+                       "loss": repr(a.loss) if a.loss is not None else None}
                 print(json.dumps(out), flush=True)
                 if a.json:
                     with open(a.json, "a") as fh:
@@ -175,7 +183,11 @@ if __name__ == "__main__":
     p.add_argument("--device-loop", action="store_true")
     p.add_argument("--prior", type=float, default=None)
     p.add_argument("--prior-scale", choices=["uniform", "subtree"], default="uniform")
+    p.add_argument("--loss", default=None, help="huber:SCALE or tukey:SCALE (flash.robust.parse)")
     a = p.parse_args()
+    if a.loss is not None:
+        from flash import robust
+        a.loss = robust.parse(a.loss)
     if a.trace:
         trace(a.trace)
     elif a.frames:
