@@ -484,6 +484,63 @@ int fsdf_get_loss(const fsdf_ctx* ctx, int32_t* kind_out, double* scale_out);
 int fsdf_eval_robust(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out /* [1+6S] */,
                      double* moments_out /* [S][21] or NULL */, double* weight_out /* [S] or NULL */);
 
+/* ---- per-point confidence weights ----------------------------------------------
+ * A loss bounds what a point does after its residual is known; a weight says
+ * what the caller knows before the pass: a depth sensor's noise at the point's
+ * range, the probability that the point belongs to the scene, the number of
+ * points a subsampled one stands for. A weight a_i >= 0 (finite) per resident
+ * point enters every sum of the robust objective above, with w = w(d*) and ρ of
+ * the context's loss: cost Σ a ρ(d*); wrench Σ 2 a w d* v; moments Σ a w v vᵀ;
+ * W_k = Σ a w. With FSDF_LOSS_SQUARE this is weighted least squares (w = 1,
+ * ρ = d²). H = 2 Σ_k JᵀM_kJ stays positive semi-definite because a >= 0. The
+ * reduction (csrc/robust.hip, its WEIGHTED instantiations) forms one product
+ * aw = a · w per point and uses it wherever w stands, and a · ρ for the cost. A
+ * point of weight 0 stays in the sums as zero terms: the summation order is a
+ * function of the cloud layout alone, as without weights, and the results are
+ * bit-identical from run to run. Weights all 1 give the bits of the same calls
+ * without weights; weights all 2^-k scale every sum exactly. The solver loops'
+ * n_points divisor is the caller's as before (the cost is c / N): a caller who
+ * wants c / Σa passes weights of mean 1.
+ *
+ * fsdf_set_point_weights: a host array of n doubles in the CALLER'S order of
+ * the resident cloud — the order of the array the cloud was set from, whatever
+ * the sort or a regroup did to the resident order. n must equal the resident
+ * cloud's size (else FSDF_ERR_ARG); a weight that is negative or not finite is
+ * FSDF_ERR_ARG, and the weights held before stay in force. weights == NULL
+ * clears: every point counts 1 again, on the code path of a context that never
+ * had weights (n is ignored). Synchronous: the array may be reused on return.
+ * fsdf_set_point_weights_device: the same from device memory, stream-ordered
+ * on the context stream, with NO validation: the caller vouches for finite,
+ * non-negative values.
+ * fsdf_get_point_weights: *set_out = 1 when weights are set, and out [n] (may
+ * be NULL) the weights in RESIDENT order — the order fsdf_permutation names
+ * and resident-order per-point outputs come in: out[i] is the caller's weight
+ * fsdf_permutation()[i] (no permutation: the caller's order). Synchronous.
+ *
+ * Weights belong to the resident cloud. Every call that makes another cloud
+ * resident clears them (fsdf_set_points, _device, _prefetched, _range*,
+ * _keyed_device): set them after the cloud. They survive fsdf_regroup_points
+ * and the auto regroup: the resident-order copy (csrc/point_weights.hip, a
+ * gather through the permutation) is rebuilt before the next robust launch,
+ * once per layout change. On a ranged or keyed cloud the two set calls return
+ * FSDF_ERR_STATE.
+ *
+ * With weights set, on a hull-only rigid scene: fsdf_eval_robust,
+ * fsdf_value_and_gradient and fsdf_value_gradient_hessian evaluate the weighted
+ * objective through the robust path, also when the loss is FSDF_LOSS_SQUARE;
+ * fsdf_descend and fsdf_descend_lm inherit it through their host loops, and
+ * fsdf_set_lm_prior applies unchanged. The refusals are the loss's: a scene
+ * with an RBF skin or a deformation is FSDF_ERR_STATE from those calls; the
+ * device loops do not serve weights (fsdf_set_solver 1 / 3 and
+ * fsdf_set_lm_solver 1 take the host loop, the required modes return
+ * FSDF_ERR_STATE). fsdf_eval, fsdf_eval_device, fsdf_eval_moments, fsdf_skin,
+ * fsdf_raycast, fsdf_eval_state_device and fsdf_state_gradient ignore weights,
+ * as they ignore the loss. Without weights every call returns the bits it
+ * returned before there were any. */
+int fsdf_set_point_weights(fsdf_ctx* ctx, const double* weights /* [n], caller order, or NULL */, int64_t n);
+int fsdf_set_point_weights_device(fsdf_ctx* ctx, const double* d_weights /* [n], caller order */, int64_t n);
+int fsdf_get_point_weights(fsdf_ctx* ctx, double* out /* [n], resident order, or NULL */, int32_t* set_out);
+
 /* ---- Gauss-Newton for RBF skins: device side -----------------------------------
  * The skins' second moments M_r above, reduced on the device
  * (csrc/skin_moments.hip): a launch of its own after the pass — the pass

@@ -289,6 +289,38 @@ function eval_robust(ctx::Context, poses::Vector{Float64})
     c[], accum, moments, weights
 end
 
+"""
+Per-point confidence weights a_i >= 0 (finite) of the resident cloud, in the order of the points
+given to set_points! (fsdf_set_point_weights): every sum of eval_robust carries a_i as a factor
+of point i's terms (cost Σ a ρ, wrench Σ 2 a w d* v, moments Σ a w v vᵀ). They belong to the
+resident cloud: every set_points! clears them. Hull-only scenes.
+"""
+set_point_weights!(ctx::Context, weights::Vector{Float64}) =
+    check(ctx.ptr, ccall((:fsdf_set_point_weights, lib), Cint, (Ptr{Void}, Ptr{Float64}, Int64),
+                         ctx.ptr, weights, length(weights)), "set_point_weights")
+
+"Every point counts 1 again (fsdf_set_point_weights with NULL)."
+clear_point_weights!(ctx::Context) =
+    check(ctx.ptr, ccall((:fsdf_set_point_weights, lib), Cint, (Ptr{Void}, Ptr{Float64}, Int64),
+                         ctx.ptr, C_NULL, 0), "set_point_weights")
+
+"The weights of the `n` resident points in resident order, or `nothing` when none are set (fsdf_get_point_weights)."
+function point_weights(ctx::Context, n::Integer)
+    set = Ref{Int32}(0)
+    out = zeros(n)
+    check(ctx.ptr, ccall((:fsdf_get_point_weights, lib), Cint, (Ptr{Void}, Ptr{Float64}, Ref{Int32}),
+                         ctx.ptr, out, set), "get_point_weights")
+    set[] != 0 ? out : nothing
+end
+
+"Weights for a GPUCost's sensed points: its passes then go through fsdf_eval_robust (hull-only scenes)."
+function set_point_weights!(f::GPUCost, weights::Vector{Float64})
+    set_point_weights!(f.ctx, weights)
+    f.robust = true
+    f.memo_x = Float64[]   # (another objective: the memoised pass no longer holds)
+    f
+end
+
 "`loss = (kind, scale)`: a robust point loss in place of the squared distance (hull-only scenes)."
 function GPUCost(manipulator::Manipulator, sensed_points::AbstractVector;
                  device::Integer=0, deformation_cost_weight=default_deformation_cost_weight,

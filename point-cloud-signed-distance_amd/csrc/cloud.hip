@@ -88,6 +88,7 @@ static int set_points_impl(fsdf_ctx* c, const double* src, int64_t n, bool devic
   int rc0 = ranged ? FSDF_OK : carry_seeds_out(c);  // (the previous cloud, still resident)
   if (rc0) return rc0;
   c->n = 0;
+  c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
   const double* d_src = src;
   if (!device_src && n > 0) {
     HIPCHECK(c, c->staging.reserve((size_t)n * 3));
@@ -175,6 +176,7 @@ static int finish_resident(fsdf_ctx* c, int64_t n, bool ranged, bool spheres_don
     c->prior_ok = true;
   }
   c->seed_pending = false;
+  c->conf_set = c->conf_stale = false;  // (a new cloud: no weights until fsdf_set_point_weights)
   c->regrouped = false;
   c->regroup_pending = true;  // (the auto regroup follows the new cloud's first iteration pass)
   c->last_pass_shape = 0;
@@ -240,6 +242,7 @@ extern "C" int fsdf_set_points_keyed_device(fsdf_ctx* c, const double* d_xyz, co
   HIPCHECK(c, hipSetDevice(c->device));
   HIPCHECK(c, hipStreamSynchronize(c->stream));
   c->n = 0;
+  c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
   HIPCHECK(c, c->cur.pts.reserve((size_t)std::max<int64_t>(n, 1) * 3 * point_bytes(c)));
   HIPCHECK(c, c->cur.perm.reserve((size_t)std::max<int64_t>(n, 1)));
   if (n > 0) {
@@ -331,6 +334,7 @@ extern "C" int fsdf_set_points_prefetched(fsdf_ctx* c) {
   rc = carry_seeds_out(c);  // (the previous cloud, still resident)
   if (rc) return rc;
   c->n = 0;
+  c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
   std::swap(c->cur, c->next);
   return finish_resident(c, n, false, true);
 }
@@ -371,6 +375,7 @@ extern "C" int fsdf_regroup_points(fsdf_ctx* c) {
   c->order_age[1] = kOrderEvery;
   c->regrouped = true;
   c->regroup_pending = false;
+  c->conf_stale = c->conf_set;  // (another layout: the weights are regathered before the next robust launch)
   return FSDF_OK;
 }
 

@@ -1,7 +1,8 @@
 // ctx.h — the context behind include/flashsdf.h, shared by the host-side
 // translation units: capi.hip (context, model, queries), cloud.hip (resident
-// cloud), pass.hip (the residual pass), iterate.hip (mechanism, one iteration),
-// descend.hip (the solver loops).
+// cloud), point_weights.hip (its per-point confidence weights), pass.hip (the
+// residual pass), iterate.hip (mechanism, one iteration), descend.hip (the
+// solver loops).
 //
 // The context owns its device and pinned memory in the buffers of
 // device_buffers.h (see the rule there: a pointer is read with get() after the
@@ -175,6 +176,12 @@ struct fsdf_ctx {
   fsdf::DevBuf<double> robust_partials, robust_rows;
   fsdf::PinnedBuf<double> h_robust;
   std::vector<double> robust_accum, robust_moments;  // the accumulator [1 + 6S] and moments [S][21] from the rows
+  // per-point confidence weights (fsdf_set_point_weights; point_weights.hip): they belong to the
+  // resident cloud (every new one clears them). conf_src [n] in the caller's order, conf_res [n]
+  // in resident order (sorted clouds: gathered through cur.perm; conf_stale: the layout changed
+  // since, regather before the next robust launch). A cloud with no permutation reads conf_src.
+  fsdf::DevBuf<double> conf_src, conf_res;
+  bool conf_set = false, conf_stale = false;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;
@@ -266,6 +273,10 @@ int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who, int what
 // robust_moments from the rows)
 int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool moments);
 void robust_rows_finish(fsdf_ctx* c, bool moments);
+// point_weights.hip: the weights in resident order for a robust launch (null: none set), regathered
+// on the context stream when the layout changed since; whether the iteration calls take the robust path
+int point_weights_resident(fsdf_ctx* c, const double** d_conf_out);
+static inline bool robust_objective(const fsdf_ctx* c) { return c->loss_kind != FSDF_LOSS_SQUARE || c->conf_set; }
 int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
           double* grad_out, bool want_pp);
 // iterate.hip (the solver loops of descend.hip run on them)

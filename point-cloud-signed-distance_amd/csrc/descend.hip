@@ -297,11 +297,15 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
   }
   // A loss other than SQUARE (fsdf_set_loss) is served by the host loop alone
   // (the device step reads the pass's least-squares accumulator).
-  const bool loss = c->loss_kind != FSDF_LOSS_SQUARE;
+  // Per-point weights (fsdf_set_point_weights) likewise.
+  const bool loss = robust_objective(c);
   if (loss && required && iteration_limit > 0)
     return fail(c, FSDF_ERR_STATE,
-                "descend: the device loop was required (fsdf_set_solver %d) but a loss is set (fsdf_set_loss kind %d: "
-                "the host loop serves it)", c->solver_device, c->loss_kind);
+                "descend: the device loop was required (fsdf_set_solver %d) but %s (the host loop serves it)",
+                c->solver_device,
+                c->conf_set ? "per-point weights are set (fsdf_set_point_weights)" :
+                c->loss_kind == FSDF_LOSS_HUBER ? "a loss is set (fsdf_set_loss kind 1)" :
+                                                  "a loss is set (fsdf_set_loss kind 2)");
   bool device_loop = c->solver_device && iteration_limit > 0 && (rigid || (c->solver_device >= 3 && declared)) &&
                      c->n > 0 && !loss;
   if (device_loop && !c->solver_tree_ok) {
@@ -552,10 +556,13 @@ extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, 
   // step's raises of a degenerate factorisation are then bounded), resident
   // points, the moments table and both solver kernels' carves within their LDS
   // A loss other than SQUARE (fsdf_set_loss): the host loop alone (mode 1 takes it, mode 2 is refused).
-  const bool loss = c->loss_kind != FSDF_LOSS_SQUARE;
+  // Per-point weights (fsdf_set_point_weights) likewise.
+  const bool loss = robust_objective(c);
   if (loss && c->lm_solver_device == 2)
-    return fail(c, FSDF_ERR_STATE, "descend_lm: the device loop was required (fsdf_set_lm_solver 2) but a loss is set "
-                                   "(fsdf_set_loss kind %d: the host loop serves it)", c->loss_kind);
+    return fail(c, FSDF_ERR_STATE, "descend_lm: the device loop was required (fsdf_set_lm_solver 2) but %s "
+                                   "(loss kind %d: the host loop serves it)",
+                c->conf_set ? "per-point weights are set (fsdf_set_point_weights)" : "a loss is set (fsdf_set_loss)",
+                c->loss_kind);
   if (rigid && c->lm_solver_device && iteration_limit > 0 && !loss) {
     const bool required = c->lm_solver_device == 2;
     if (required && !(damping > 0.0))

@@ -291,10 +291,15 @@ bool robust_fit(int S);
 size_t robust_partials_len(int64_t n, int S);
 // n > 0, robust_fit(S), a valid loss (kind, scale: robust_impl.h). d_pts: the
 // resident cloud (precision 64 / 32; all arithmetic fp64); d_rows [S][29]
-// (moments) or [S][8]. A k* outside [0, S) contributes nothing.
+// (moments) or [S][8]. A k* outside [0, S) contributes nothing. d_conf: null, or
+// [n] per-point confidence weights in resident order (fp64 in either precision):
+// the WEIGHTED instantiations, aw = a · w in place of w and a · ρ in place of ρ.
 hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
-                         const double* d_grad, int64_t n, int S, int kind, double scale, double* d_partials,
-                         double* d_rows, hipStream_t s);
+                         const double* d_grad, const double* d_conf, int64_t n, int S, int kind, double scale,
+                         double* d_partials, double* d_rows, hipStream_t s);
+// res[i] = src[perm[i]] over n doubles (point_weights.hip: a per-point side array
+// into resident order; an index outside [0, n) reads as 0)
+hipError_t launch_gather_f64(const double* d_src, const int32_t* d_perm, int64_t n, double* d_res, hipStream_t s);
 
 // ---- second moments of RBF skins (skin_moments.hip) ----------------------------
 // Per skin r of n centres, m = 4n + 4: M_r [m][m] = Σ_{p: k*(p) = r's surface}

@@ -255,7 +255,8 @@ double g_host_t[8];  // (ctx.h: the host loop's clocks, printed by fsdf_descend)
 long g_host_n;
 #endif
 
-// With a loss other than SQUARE set (fsdf_set_loss): the same iteration on the
+// With a loss other than SQUARE set (fsdf_set_loss), or per-point weights
+// (fsdf_set_point_weights: then also under SQUARE): the same iteration on the
 // robust objective Σρ(d*) — the pass with k*, d*, ∇d* in resident order, the
 // robust launch (robust.hip) in place of the pass's own sums, and the same
 // chain rule on the accumulator assembled from its rows. The auto regroup is
@@ -265,8 +266,8 @@ static int robust_iteration(fsdf_ctx* c, const double* x, double* cost_out, doub
                             const char* who) {
   if (c->lm.R > 0 || c->mech.n_deform > 0)
     return fail(c, FSDF_ERR_STATE,
-                "%s: the loss set by fsdf_set_loss (kind %d) serves rigid scenes (no RBF skin, no deformation)", who,
-                c->loss_kind);
+                "%s: the loss set by fsdf_set_loss (kind %d)%s serves rigid scenes (no RBF skin, no deformation)", who,
+                c->loss_kind, c->conf_set ? " and the weights of fsdf_set_point_weights" : "");
   int rc = iteration_prepare(c, x, who);
   if (rc) return rc;
   auto& M = c->mech;
@@ -297,7 +298,7 @@ extern "C" int fsdf_value_and_gradient(fsdf_ctx* c, const double* x, double* cos
   if (!c) return FSDF_ERR_ARG;
   HOST_STAMP(0);
   if (!x || !cost_out || !grad_out) return fail(c, FSDF_ERR_ARG, "value_and_gradient: null argument");
-  if (c->loss_kind != FSDF_LOSS_SQUARE) return robust_value_and_gradient(c, x, cost_out, grad_out);
+  if (robust_objective(c)) return robust_value_and_gradient(c, x, cost_out, grad_out);
   int rc = iteration_prepare(c, x, "value_and_gradient");
   if (rc) return rc;
   auto& M = c->mech;
@@ -339,7 +340,7 @@ extern "C" int fsdf_value_gradient_hessian(fsdf_ctx* c, const double* x, double*
   if (!c) return FSDF_ERR_ARG;
   if (!x || !cost_out || !grad_out || !hess_out)
     return fail(c, FSDF_ERR_ARG, "value_gradient_hessian: null argument");
-  if (c->loss_kind != FSDF_LOSS_SQUARE)
+  if (robust_objective(c))
     return robust_iteration(c, x, cost_out, grad_out, hess_out, "value_gradient_hessian");
   const bool rigid = c->lm.R == 0 && c->mech.n_deform == 0;
   if (!rigid && !c->lm_skins)

@@ -537,6 +537,10 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
   double* d_rows = c->robust_rows.get();
   double* h_rows = c->h_robust.get();
   double* d_accum = c->model.accum.get();
+  // (the per-point weights in resident order, regathered when the layout changed since; null: none set)
+  const double* d_conf = nullptr;
+  rc = point_weights_resident(c, &d_conf);
+  if (rc) return rc;
   // (3) launch: the pass with k*, d* and ∇d* in resident order (no permutation), the robust sums, their read-back
   rc = run_pass(c, poses, d_pts, n, d_accum, d_kstar, d_d, d_grad, nullptr, true);
   if (rc) return rc;
@@ -545,7 +549,7 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
     memset(h_rows, 0, rlen * sizeof(double));
     return FSDF_OK;
   }
-  HIPCHECK(c, fsdf::launch_robust(c->precision, moments, d_pts, d_kstar, d_d, d_grad, n, S, c->loss_kind,
+  HIPCHECK(c, fsdf::launch_robust(c->precision, moments, d_pts, d_kstar, d_d, d_grad, d_conf, n, S, c->loss_kind,
                                   c->loss_scale, d_partials, d_rows, c->stream));
   HIPCHECK(c, hipMemcpyAsync(h_rows, d_rows, rlen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   return FSDF_OK;

@@ -22,6 +22,12 @@
 // partial. No floating-point atomics: the summation order is a function of
 // (n, S, the resident order, k*) alone, so results are bit-identical from run
 // to run.
+//
+// WEIGHTED (fsdf_set_point_weights): a confidence a_i >= 0 per resident point,
+// conf[i] in resident order (fp64 also in fp32 contexts). One product
+// aw = a · w stands wherever w does (the moments, wrench_scale(aw, d), Σw), and
+// a · ρ in the cost. A point of weight 0 stays in the sums as zero terms: the
+// summation order is the unweighted kernel's, a function of the layout alone.
 
 #include <hip/hip_runtime.h>
 
@@ -64,13 +70,14 @@ size_t robust_partials_len(int64_t n, int S) {
 extern __shared__ __attribute__((aligned(16))) double robust_tab[];  // [waves][S][LEN]
 
 // blockDim.x / 64 waves; run is a multiple of them
-template <typename T, bool MOMENTS>
+template <typename T, bool MOMENTS, bool WEIGHTED>
 __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restrict__ pts,
                                                               const int32_t* __restrict__ kstar,
                                                               const double* __restrict__ dstar,
                                                               const double* __restrict__ grad, int64_t n, int S,
                                                               int run, int kind, double scale,
-                                                              double* __restrict__ partials) {
+                                                              double* __restrict__ partials,
+                                                              const double* __restrict__ conf) {
   constexpr int LEN = MOMENTS ? kRobustLen : kRobustTail;
   constexpr int M0 = LEN - kRobustTail;  // the wrench's first entry; Σρ at M0 + 6, Σw at M0 + 7
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
@@ -126,7 +133,8 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
       v[3] = py * v[2] - pz * v[1];
       v[4] = pz * v[0] - px * v[2];
       v[5] = px * v[1] - py * v[0];
-      const double w = robust::weight(kind, scale, d);
+      const double a = WEIGHTED ? conf[i] : 1.0;
+      const double w = WEIGHTED ? a * robust::weight(kind, scale, d) : robust::weight(kind, scale, d);  // aw
       if (MOMENTS) {
         int e = 0;
 #pragma unroll
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
       const double t = robust::wrench_scale(w, d);
 #pragma unroll
       for (int a = 0; a < 6; ++a) acc[M0 + a] += t * v[a];
-      acc[M0 + 6] += robust::rho(kind, scale, d);
+      acc[M0 + 6] += WEIGHTED ? a * robust::rho(kind, scale, d) : robust::rho(kind, scale, d);
       acc[M0 + 7] += w;
       ck = k;
     }
@@ -156,24 +164,31 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
 }
 
 hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
-                         const double* d_grad, int64_t n, int S, int kind, double scale, double* d_partials,
-                         double* d_rows, hipStream_t s) {
+                         const double* d_grad, const double* d_conf, int64_t n, int S, int kind, double scale,
+                         double* d_partials, double* d_rows, hipStream_t s) {
   if (n <= 0 || !robust_fit(S) || !robust::valid(kind, scale) || !d_pts || !d_kstar || !d_d || !d_grad ||
       !d_partials || !d_rows)
     return hipErrorInvalidValue;
   const int groups = robust_groups(n), run = (int)robust_run(n), waves = robust_waves(S), block = 64 * waves;
   const int len = moments ? kRobustLen : kRobustTail;
   const size_t lds = (size_t)waves * S * len * sizeof(double);
-#define FSDF_ROBUST_LAUNCH(T, M)                                                                              \
-  hipLaunchKernelGGL((robust_kernel<T, M>), dim3(groups), dim3(block), lds, s, (const T*)d_pts, d_kstar, d_d, \
-                     d_grad, n, S, run, kind, scale, d_partials)
+#define FSDF_ROBUST_LAUNCH(T, M, W)                                                                              \
+  hipLaunchKernelGGL((robust_kernel<T, M, W>), dim3(groups), dim3(block), lds, s, (const T*)d_pts, d_kstar, d_d, \
+                     d_grad, n, S, run, kind, scale, d_partials, d_conf)
+#define FSDF_ROBUST_LAUNCH_M(T, W)              \
+  do {                                          \
+    if (moments) FSDF_ROBUST_LAUNCH(T, true, W); \
+    else FSDF_ROBUST_LAUNCH(T, false, W);        \
+  } while (0)
+  // (d_conf null: the unweighted instantiations, which never read it)
   if (precision == 64) {
-    if (moments) FSDF_ROBUST_LAUNCH(double, true);
-    else FSDF_ROBUST_LAUNCH(double, false);
+    if (d_conf) FSDF_ROBUST_LAUNCH_M(double, true);
+    else FSDF_ROBUST_LAUNCH_M(double, false);
   } else {
-    if (moments) FSDF_ROBUST_LAUNCH(float, true);
-    else FSDF_ROBUST_LAUNCH(float, false);
+    if (d_conf) FSDF_ROBUST_LAUNCH_M(float, true);
+    else FSDF_ROBUST_LAUNCH_M(float, false);
   }
+#undef FSDF_ROBUST_LAUNCH_M
 #undef FSDF_ROBUST_LAUNCH
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;

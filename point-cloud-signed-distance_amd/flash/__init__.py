@@ -15,7 +15,7 @@ from .robust import Huber, Tukey
 __all__ = ["BodyGeometry", "ConvexGeometry", "DeformableInterpolatingSkin", "InterpolatingGeometry",
            "Manipulator", "ManipulatorState", "RigidInterpolatingSkin", "SceneSkin", "hull_poses",
            "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError",
-           "LevenbergMarquardt", "Huber", "Tukey"]
+           "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights"]
 
 
 def __getattr__(name):
@@ -29,6 +29,9 @@ def __getattr__(name):
     if name == "LevenbergMarquardt":  # the opt-in second-order tracking solver
         from .tracking import LevenbergMarquardt
         return LevenbergMarquardt
+    if name == "depth_noise_weights":  # per-point confidence weights from a depth sensor's axial noise
+        from .depthsensors import depth_noise_weights
+        return depth_noise_weights
     if name == "DepthSensors":
         from . import depthsensors
         return depthsensors

@@ -125,6 +125,9 @@ _PROTOS = {
     "fsdf_set_loss_ref": (c_int32, [c_void_p, c_int32, POINTER(c_double)]),
     "fsdf_get_loss": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_double)]),
     "fsdf_eval_robust": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p, c_void_p]),
+    "fsdf_set_point_weights": (c_int32, [c_void_p, c_void_p, c_int64]),
+    "fsdf_set_point_weights_device": (c_int32, [c_void_p, c_void_p, c_int64]),
+    "fsdf_get_point_weights": (c_int32, [c_void_p, c_void_p, POINTER(c_int32)]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -484,6 +487,40 @@ class Context:
         check(self._lib.fsdf_eval_robust(self._ctx, ptr(p), ctypes.byref(cost), ptr(accum), ptr(mom), ptr(wts)),
               self._ctx, "eval_robust")
         return cost.value, accum, mom, wts
+
+    def set_point_weights(self, weights):
+        """fsdf_set_point_weights: one confidence weight a_i >= 0 (finite) per
+        resident point, in the order of the array the cloud was set from
+        (whatever the sort or a regroup did) — a factor of that point's terms
+        in every sum of eval_robust, value_and_gradient,
+        value_gradient_hessian, descend and descend_lm (hull-only rigid scenes;
+        the robust path, also without a loss). None clears them. They belong
+        to the resident cloud: every set_points* clears them."""
+        if weights is None:
+            check(self._lib.fsdf_set_point_weights(self._ctx, None, 0), self._ctx, "set_point_weights")
+            return
+        w = np.ascontiguousarray(weights, np.float64)
+        if w.ndim != 1:
+            raise ValueError(f"set_point_weights: one weight per point, got shape {w.shape}")
+        check(self._lib.fsdf_set_point_weights(self._ctx, ptr(w), w.shape[0]), self._ctx, "set_point_weights")
+
+    def set_point_weights_device(self, dev_ptr: int, n: int):
+        """fsdf_set_point_weights_device: the same from device memory (caller
+        order), stream-ordered and NOT validated."""
+        check(self._lib.fsdf_set_point_weights_device(self._ctx, c_void_p(dev_ptr), n), self._ctx,
+              "set_point_weights_device")
+
+    def point_weights(self):
+        """fsdf_get_point_weights: the weights in RESIDENT order (entry i is the
+        caller's weight permutation()[i]), or None when none are set."""
+        flag = c_int32(0)
+        check(self._lib.fsdf_get_point_weights(self._ctx, None, ctypes.byref(flag)), self._ctx, "get_point_weights")
+        if not flag.value:
+            return None
+        out = np.empty(self.n, np.float64)
+        check(self._lib.fsdf_get_point_weights(self._ctx, ptr(out), ctypes.byref(flag)), self._ctx,
+              "get_point_weights")
+        return out
 
     def eval_skin_moments(self, poses):
         """fsdf_eval_skin_moments: one pass over the resident cloud and the

@@ -9,6 +9,10 @@
 The per-ray secant march runs in raycast_kernel (fsdf_raycast), one lane per
 ray, on the same scene SDF as the residual pass. LCMGL drawing (:36-52,
 :120-135) is out of scope.
+
+depth_noise_weights (not in the reference): per-point confidence weights from
+a structured-light sensor's axial noise model, for estimate_state / Tracker /
+track (`weights=`).
 """
 from __future__ import annotations
 
@@ -61,3 +65,32 @@ def raycast_points(surface: SceneSkin, sensor: DepthSensor, tform: Transform) ->
 
 def raycast(state: ManipulatorState, sensor: DepthSensor, tform: Transform, device: int = 0) -> np.ndarray:
     return raycast_points(skin(state, device), sensor, tform)
+
+
+def depth_noise_weights(points, origin, axis, sigma0: float = 0.0012, k: float = 0.0019, z0: float = 0.4):
+    """Confidence weights (σ0 / σ(z))² in (0, 1] for the points of a depth cloud,
+    σ(z) = σ0 + k (z − z0)² the axial noise of a structured-light camera at
+    range z: the model of Nguyen, Izadi and Lovell, "Modeling Kinect sensor
+    noise for improved 3D reconstruction and tracking" (3DIMPVT 2012), with
+    their Kinect parameters as defaults (metres) — the caller's to set for
+    another sensor. points [n, 3] in the world frame; origin [3] the sensor's
+    position, axis [3] its optical axis (any length > 0); z = (p − origin) · axis
+    / |axis| is the range along the axis. 1 at z = z0, decreasing beyond it.
+    Evaluated as (σ0 / (σ0 + k (z − z0)²))², in that order. The weights are not
+    normalised: the solvers divide the cost by the point count as before, so
+    rescale to mean 1 where the cost per unit of weight matters."""
+    p = np.asarray(points, np.float64)
+    o, a = np.asarray(origin, np.float64), np.asarray(axis, np.float64)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError(f"depth_noise_weights: points must be [n, 3], got {p.shape}")
+    if o.shape != (3,) or a.shape != (3,):
+        raise ValueError(f"depth_noise_weights: origin and axis must be [3], got {o.shape} and {a.shape}")
+    norm = float(np.sqrt(a @ a))
+    if not (np.isfinite(norm) and norm > 0.0):
+        raise ValueError("depth_noise_weights: the axis must be finite and not zero")
+    if not (sigma0 > 0.0 and k >= 0.0 and np.isfinite(sigma0) and np.isfinite(k) and np.isfinite(z0)):
+        raise ValueError("depth_noise_weights: sigma0 > 0, k >= 0 and z0 must be finite")
+    z = (p - o) @ (a / norm)
+    dz = z - z0
+    r = sigma0 / (sigma0 + k * (dz * dz))
+    return r * r

@@ -143,6 +143,28 @@ class CostFunctor:
         # descend and descend_lm (fsdf_set_loss; native rigid scenes)
         self.loss = None
         self.set_loss(loss)
+        # point_weights: one confidence weight per sensed point (set_point_weights;
+        # None: every point counts 1), dropped whenever the sensed points change
+        self.point_weights = None
+
+    def set_point_weights(self, weights):
+        """Per-point confidence weights a_i >= 0 of this functor's objective,
+        one per sensed point in the order of `sensed_points` (None: none):
+        Σ a ρ(d*) in place of Σ ρ(d*), its gradient and the Gauss-Newton Hessian
+        (fsdf_set_point_weights; the robust reduction, also without a loss).
+        Native rigid scenes only. They belong to the sensed cloud:
+        set_sensed_points drops them. per_point and the least-squares queries
+        of the context are not affected."""
+        if weights is not None:
+            if not (self._native and self.rigid):
+                raise NotImplementedError(
+                    "point weights: they serve native rigid scenes (no RBF skin, no deformation)")
+            weights = np.array(weights, np.float64, copy=True).reshape(-1)
+            if len(weights) != len(self.sensed_points):
+                raise ValueError(f"point weights: {len(weights)} weights for {len(self.sensed_points)} sensed points")
+        self._ensure_resident()
+        self.ctx.set_point_weights(weights)  # (refused: the earlier weights stay, here too)
+        self.point_weights = weights
 
     def set_loss(self, loss):
         """The robust point loss of this functor's objective (flash.robust;
@@ -178,6 +200,7 @@ class CostFunctor:
         prefetch_sensed_points last is made resident from its device copy."""
         pre, src = getattr(self, "_prefetched", None), getattr(self, "_prefetched_src", None)
         self._prefetched = self._prefetched_src = None
+        self.point_weights = None  # (another cloud: the library drops its copy with the old one)
         if pre is not None and sensed_points is src:  # (the object prefetched: its device copy)
             self.sensed_points = pre
             self.ctx.set_points_prefetched()
@@ -207,6 +230,8 @@ class CostFunctor:
         if getattr(self.manipulator, "_resident_cloud", None) != self._resident:
             self.ctx.set_points(self.sensed_points)
             self.manipulator._resident_cloud = self._resident
+            if getattr(self, "point_weights", None) is not None:  # (they left with the cloud)
+                self.ctx.set_point_weights(self.point_weights)
 
     def _pass(self, x, per_point=False):
         unflatten(self.state, x)
@@ -217,7 +242,7 @@ class CostFunctor:
         return c + _regularizer(self.state, self.weight), accum, extras
 
     def __call__(self, x) -> float:
-        if self.loss is not None:  # (the robust objective: the native iteration's cost)
+        if self.loss is not None or self.point_weights is not None:  # (the robust / weighted objective: the native iteration's cost)
             return self.value_and_gradient(x)[0]
         return self._pass(x)[0]
 

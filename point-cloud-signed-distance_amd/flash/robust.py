@@ -101,3 +101,40 @@ def parse(spec):
     if name not in kinds or not scale:
         raise ValueError(f"loss {spec!r}: expected huber:SCALE or tukey:SCALE")
     return kinds[name](float(scale))
+
+
+def weighted_sums(points, kstar, d, grad, n_surfaces, loss=None, weights=None):
+    """The per-surface sums of the (weighted) robust objective in plain numpy,
+    from per-point outputs (include/flashsdf.h "per-point confidence
+    weights"): with a = weights (None: 1), w = w(d) and ρ of `loss` (None:
+    w = 1, ρ = d²), v = (∇d, p × ∇d) and aw = a · w, over the points with
+    k* = k:
+        cost [S] Σ a ρ;  wrench [S, 6] Σ 2 (aw d) v;  moments [S, 21] Σ aw v vᵀ
+        (upper triangle, row-major);  W [S] Σ aw.
+    The per-point factors are formed as csrc/robust.hip forms them (one product
+    aw, wrench scale 2 (aw d), a · ρ); the sums are numpy's, in the dtype of `d`
+    (float64 by default; a test may pass numpy.longdouble)."""
+    dd = _residuals(d)
+    t = dd.dtype.type
+    P, G = np.asarray(points, dd.dtype), np.asarray(grad, dd.dtype)
+    k = np.asarray(kstar)
+    w = np.ones_like(dd) if loss is None else loss.weight(dd)
+    rho = dd * dd if loss is None else loss.rho(dd)
+    if weights is not None:
+        a = np.asarray(weights, dd.dtype)
+        if a.shape != dd.shape:
+            raise ValueError(f"weighted_sums: {a.shape} weights for {dd.shape} points")
+        w, rho = a * w, a * rho
+    v = np.concatenate([G, np.cross(P, G)], axis=1)
+    term = v * (t(2) * (w * dd))[:, None]
+    iu = np.triu_indices(6)
+    S = int(n_surfaces)
+    cost, wrench = np.zeros(S, dd.dtype), np.zeros((S, 6), dd.dtype)
+    moments, W = np.zeros((S, 21), dd.dtype), np.zeros(S, dd.dtype)
+    for s in np.unique(k):
+        if s < 0 or s >= S:
+            continue
+        sel = k == s
+        cost[s], wrench[s], W[s] = rho[sel].sum(), term[sel].sum(0), w[sel].sum()
+        moments[s] = np.einsum("ni,nj->ij", v[sel] * w[sel, None], v[sel])[iu]
+    return cost, wrench, moments, W

@@ -193,7 +193,17 @@ def _default_solver(manipulator):
     return NaiveSolver(num_states(manipulator), rate=0.1, max_step=0.5, iteration_limit=30)
 
 
-def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, loss=None):
+def _frame_weights(weights, points):
+    """weights as estimate_state / Tracker / track take them: None, one array
+    per call, or a callable points -> weights applied to the frame's cloud."""
+    if weights is None:
+        return None
+    if callable(weights):
+        weights = weights(points)
+    return np.asarray(weights, np.float64).reshape(-1)
+
+
+def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, loss=None, weights=None):
     """wrapped_cost (src/tracking.jl:16-21) over a CostFunctor, then optimize!.
     Without a callback, a NaiveSolver runs natively (fsdf_descend: the same
     arithmetic, no Python round trip per iteration), and so does a
@@ -206,10 +216,16 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, l
     the functor (CostFunctor.set_loss) before anything runs, so every path
     above — the native loops, the Python loops, the callback's cost — is over
     the robust objective Σρ(d*)/N. The device-resident loops do not serve a
-    loss: device_loop=True runs the host loop, "require" is refused."""
+    loss: device_loop=True runs the host loop, "require" is refused.
+    weights (one confidence weight per point of the functor's cloud; None: the
+    functor as it is): handed to the functor (CostFunctor.set_point_weights)
+    before anything runs, under the loss's rules. n_points stays the divisor:
+    pass weights of mean 1 for c / Σa."""
     n = max(n_points, 1)
     if loss is not None:
         cost.set_loss(loss)
+    if weights is not None:
+        cost.set_point_weights(weights)
     if callback is None and type(solver) is NaiveSolver and cost._native:
         x0 = np.asarray(x_estimated, np.float64)
         div = solver.precondition_divisors
@@ -257,17 +273,21 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, l
 
 
 def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callback=None, solver=None,
-                   device: int = 0, precision: int = 64, loss=None):
+                   device: int = 0, precision: int = 64, loss=None, weights=None):
     """Tracking.estimate_state (src/tracking.jl:8-27). Returns the solution x.
 
     The default callback accepts (x, c): the reference's default `x -> ()` is
     called with two arguments (src/tracking.jl:9 vs :19) and would throw.
     loss: a robust point loss (flash.robust.Huber / Tukey) in place of the
-    squared distance — native rigid scenes; the callback then sees Σρ(d*)."""
+    squared distance — native rigid scenes; the callback then sees Σρ(d*).
+    weights: one confidence weight >= 0 per sensed point (an array, or a
+    callable points -> weights, e.g. depthsensors.depth_noise_weights bound to
+    a sensor pose): the objective is Σ a ρ(d*) / N — native rigid scenes; set
+    after the cloud is resident."""
     pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
     solver = solver or _default_solver(manipulator)
     cost = CostFunctor(manipulator, pts, device=device, precision=precision)
-    return _optimize(cost, len(pts), x_estimated, callback, solver, loss=loss)
+    return _optimize(cost, len(pts), x_estimated, callback, solver, loss=loss, weights=_frame_weights(weights, pts))
 
 
 def notebook_frame_solver(manipulator):
@@ -283,27 +303,34 @@ class Tracker:
     iteration are recorded (host FK + pass + chain rule, end to end)."""
 
     def __init__(self, manipulator: Manipulator, state: ManipulatorState | None = None, solver=None,
-                 device: int = 0, precision: int = 64, loss=None):
+                 device: int = 0, precision: int = 64, loss=None, weights=None):
         self.manipulator = manipulator
         self.state = state if state is not None else ManipulatorState(manipulator)
         self.solver = solver or notebook_frame_solver(manipulator)
         self.cost = CostFunctor(manipulator, np.zeros((0, 3)), device=device, precision=precision)
         self.loss = loss  # a robust point loss for every frame (flash.robust; None: least squares)
+        # per-point confidence weights: a callable points -> weights applied to every frame (an
+        # array fits one frame only: give it to step); None: every point counts 1
+        self.weights = weights
         self.frame_ms: list[float] = []
         self.set_points_ms: list[float] = []
         self.iterations: list[int] = []
 
-    def step(self, sensed_points, callback=None, next_points=None) -> np.ndarray:
+    def step(self, sensed_points, callback=None, next_points=None, weights=None) -> np.ndarray:
         """gradient_descent!(state, model, sensed_points): one frame.
         next_points (optional): the next frame's cloud, whose upload then runs
-        under this frame's solver iterations (CostFunctor.prefetch_sensed_points)."""
+        under this frame's solver iterations (CostFunctor.prefetch_sensed_points).
+        weights (optional): this frame's confidence weights, an array or a
+        callable points -> weights; None: the Tracker's own. They are set after
+        the frame's cloud is resident, prefetched or not."""
         pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
         t0 = time.perf_counter()
         self.cost.set_sensed_points(sensed_points)  # (the object itself: a prefetched frame is matched by identity)
         if next_points is not None:
             self.cost.prefetch_sensed_points(next_points)
         t1 = time.perf_counter()
-        x = _optimize(self.cost, len(pts), flatten(self.state), callback, self.solver, loss=self.loss)
+        w = _frame_weights(self.weights if weights is None else weights, pts)
+        x = _optimize(self.cost, len(pts), flatten(self.state), callback, self.solver, loss=self.loss, weights=w)
         unflatten(self.state, x)
         t2 = time.perf_counter()
         self.set_points_ms.append((t1 - t0) * 1e3)
@@ -318,12 +345,14 @@ class Tracker:
 
 
 def track(manipulator: Manipulator, frames, state: ManipulatorState | None = None, solver=None, callback=None,
-          device: int = 0, precision: int = 64, loss=None):
+          device: int = 0, precision: int = 64, loss=None, weights=None):
     """for event in log: gradient_descent!(state, model, sensed_points)
     (examples/irb_and_squishable.ipynb cells 11-12). `frames` yields sensed
     clouds ([n,3]); returns (the per-frame solutions [F, n_states], the Tracker).
-    loss: a robust point loss for every frame (flash.robust)."""
-    tr = Tracker(manipulator, state, solver, device, precision, loss=loss)
+    loss: a robust point loss for every frame (flash.robust).
+    weights: a callable points -> weights applied to every frame (or one array,
+    where every frame has as many points)."""
+    tr = Tracker(manipulator, state, solver, device, precision, loss=loss, weights=weights)
     xs = []
     it = iter(frames)
     cur = next(it, None)

@@ -21,7 +21,12 @@ subtree: W · N / points nearest a surface of the subtree; f is then the wrapped
 objective's, the prior included). --loss huber:0.02 | tukey:0.05 gives every
 frame (and, without --frames, every timed call) that robust point loss
 (fsdf_set_loss: f is then Σρ/N, the LM frames run the host loop); the table
-also carries the error over the three base joints of each arm.
+also carries the error over the three base joints of each arm. --weights
+depth | random gives the resident cloud per-point confidence weights
+(fsdf_set_point_weights; set again after every cloud swap): depth the axial
+noise model of flash.depth_noise_weights for a sensor 1.5 m from the cloud's
+centre looking along +x, random uniform in [0, 2] with one in ten exactly 0 —
+the calls then run the weighted robust reduction, also without --loss.
 
 And for the kernels' own times a kernel trace of the Hessian calls alone
 (no counters in the same run):
@@ -45,6 +50,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "point-cloud-signed-distance_amd"))
 
 
+def point_weights(kind, pts):
+    """The --weights array for a cloud (None: no weights)."""
+    if kind is None:
+        return None
+    if kind == "depth":
+        from flash import depth_noise_weights
+        return depth_noise_weights(pts, pts.mean(0) - [1.5, 0.0, 0.0], [1.0, 0.0, 0.0])
+    r = np.random.default_rng(99)
+    w = r.uniform(0.0, 2.0, len(pts))
+    w[r.random(len(pts)) < 0.1] = 0.0
+    return w
+
+
 def run(a):
     import torch  # noqa: F401  (the HIP runtime torch loads, before libflashsdf)
     from flash import Models, synthetic
@@ -56,6 +74,8 @@ def run(a):
         q_true, q = synthetic.perturbed_configuration(m, 1234)
         q = np.asarray(q, np.float64)
         cf = CostFunctor(m, synthetic.depth_cloud(m, q_true, n, seed=1234 + 17), loss=a.loss)
+        if a.weights:
+            cf.set_point_weights(point_weights(a.weights, cf.sensed_points))
         for _ in range(5):  # the cloud's first pass, the regroup, the block order / plan, allocations
             cf.value_and_gradient(q)
             cf.value_gradient_hessian(q)
@@ -69,7 +89,7 @@ def run(a):
             cf.value_gradient_hessian(q)
             vgh.append((time.perf_counter() - t0) * 1e6)
         out = {"model": model, "points": n, "reps": a.reps, "pass_kernel": cf.ctx.pass_kernel_name(),
-               "loss": repr(a.loss) if a.loss is not None else None,
+               "loss": repr(a.loss) if a.loss is not None else None, "weights": a.weights,
                "value_gradient_hessian_us": statistics.median(vgh),
                "value_gradient_hessian_us_p10_p90": [float(np.percentile(vgh, 10)), float(np.percentile(vgh, 90))]}
         if vg:
@@ -94,6 +114,7 @@ def frames(a):
         q = np.asarray(q, np.float64)
         pts = synthetic.depth_cloud(m, q_true, n, seed=1234 + 17)
         cf = CostFunctor(m, pts, loss=a.loss)
+        w = point_weights(a.weights, pts)
         f_true = cf.value_and_gradient(np.asarray(q_true, np.float64))[0] / n
         # the three base joints of each arm (IRB140: six revolute joints per arm, in arm order)
         base = np.array([j for j in range(len(q)) if j % 6 < 3])
@@ -112,6 +133,8 @@ def frames(a):
                 for _ in range(a.frames + 1):
                     t0 = time.perf_counter()
                     cf.set_sensed_points(pts)
+                    if w is not None:
+                        cf.set_point_weights(w)
                     if name == "naive":
                         x, f, its = cf.descend(q, 30, 0.1, 0.5, 1e-3, None, float(n))
                     else:
@@ -123,7 +146,7 @@ def frames(a):
                        "prior_scale": a.prior_scale if a.prior is not None else None,
                        "max_abs_q_error": float(np.abs(x - q_true).max()),
                        "max_abs_base_joint_error": float(np.abs(x - q_true)[base].max()),
-                       "loss": repr(a.loss) if a.loss is not None else None}
+                       "loss": repr(a.loss) if a.loss is not None else None, "weights": a.weights}
                 print(json.dumps(out), flush=True)
                 if a.json:
                     with open(a.json, "a") as fh:
@@ -184,6 +207,8 @@ if __name__ == "__main__":
     p.add_argument("--prior", type=float, default=None)
     p.add_argument("--prior-scale", choices=["uniform", "subtree"], default="uniform")
     p.add_argument("--loss", default=None, help="huber:SCALE or tukey:SCALE (flash.robust.parse)")
+    p.add_argument("--weights", choices=["depth", "random"], default=None,
+                   help="per-point confidence weights for the resident cloud (fsdf_set_point_weights)")
     a = p.parse_args()
     if a.loss is not None:
         from flash import robust
