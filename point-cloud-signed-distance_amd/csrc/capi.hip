@@ -359,9 +359,10 @@ extern "C" int fsdf_set_surfaces(fsdf_ctx* c, const fsdf_surface* surfs, int32_t
   auto room = [](auto& buf, size_t n) { return n ? buf.reserve(n) : hipSuccess; };  // (an empty array: no buffer)
   PosedBuffers& pb = c->posed;
   HIPCHECK(c, room(pb.verts_w, (size_t)V * 4 * tsz));
-  HIPCHECK(c, room(pb.hscale_w, (size_t)K * tsz));
   HIPCHECK(c, pb.planes_w.reserve((size_t)std::max(F, 1) * 4 * tsz));
-  HIPCHECK(c, room(pb.spheres_w, (size_t)K * fsdf::kBoundFloats));
+  // (row K is the sentinel; zeroed here for scenes without hulls, which no pose launch writes)
+  HIPCHECK(c, pb.hull_rows.reserve((size_t)(K + 1) * fsdf::kHullRowBytes));
+  if (K == 0) HIPCHECK(c, hipMemset(pb.hull_rows.get(), 0, fsdf::kHullRowBytes));
   HIPCHECK(c, pb.screen_w.reserve((size_t)std::max(F + K, 1) * 4));
   if (planes64) {
     HIPCHECK(c, pb.image_w.reserve(chunks * 16));
@@ -408,9 +409,8 @@ extern "C" int fsdf_set_surfaces(fsdf_ctx* c, const fsdf_surface* surfs, int32_t
   lm.rbf_row_off = mb.rbf_row_off.get();
   lm.rbf_acc_off = mb.rbf_acc_off.get();
   c->pm.planes_w = pb.planes_w.get();
-  c->pm.spheres_w = pb.spheres_w.get();
+  c->pm.hull_rows = pb.hull_rows.get();
   c->pm.verts_w = pb.verts_w.get();
-  c->pm.hscale_w = pb.hscale_w.get();
   c->pm.screen_w = pb.screen_w.get();
   c->pm.image_w = pb.image_w.get();
   // per-pass RBF rows (f64 contexts read the f64 rows)

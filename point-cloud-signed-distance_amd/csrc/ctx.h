@@ -41,8 +41,8 @@ struct ModelBuffers {
 };
 // storage of one fsdf::PosedModel (T arrays in bytes)
 struct PosedBuffers {
-  fsdf::DevBuf<unsigned char> verts_w, hscale_w, planes_w, image_w;
-  fsdf::DevBuf<float> spheres_w, screen_w;
+  fsdf::DevBuf<unsigned char> verts_w, hull_rows, planes_w, image_w;
+  fsdf::DevBuf<float> screen_w;
 };
 // storage of fsdf::ChunkOutputs and the plan kernel's scratch
 struct ChunkBuffers {

@@ -19,10 +19,12 @@
 //
 //   posed model (rewritten by every evaluation; T = double or float)
 //     planes_w  [F][4]  T       world plane
-//     spheres_w [K][20] f32     culling bounds: world centroid + radius, then the world
-//                               oriented box: (centre, 0), 3 x (body axis i, half extent i)
+//     hull_rows [K+1]   96 B    the hull table (pose_impl.h HullRow): world centroid + radius
+//                               and the world oriented box — (centre, 0), 3 x (body axis i,
+//                               half extent i) — as f32 culling bounds, face_off[k], vert_off[k],
+//                               the certificate scale max_v |v|_1 over the hull's world vertices
+//                               (f64); row K: the offsets' ends and the culling-margin scale
 //     verts_w   [V][4]  T       world vertices (support/optimality certificate)
-//     hscale_w  [K]     T       max_v |v|_1 over the hull's world vertices
 //     screen_w  [F+K][4] f32    fp32 screening planes, hull-centred, in face pairs:
 //                               hull k's pair j at slots face_off[k]+k+2j (32 B):
 //                               (nx_a nx_b ny_a ny_b nz_a nz_b -d'_a -d'_b), a = 2j,
@@ -78,7 +80,7 @@ constexpr int kRedInStageMinBytes = (64 * 6 + 2) * 8 + 64 * 3 * 8;
 
 constexpr int kBlock = 256;
 constexpr int kPassBlock = 256;    // pass-kernel workgroup: 4 waves of 64
-constexpr int kBoundFloats = 20;   // spheres_w row (sphere + oriented box)
+constexpr int kHullRowBytes = 96;  // a row of the posed hull table (pose_impl.h HullRow)
 constexpr int kLdsPerCu = 163840;  // gfx950 LDS per CU
 constexpr int kMaxLds = 163840;    // LDS a workgroup may declare (gfx950)
 constexpr int kMaxHulls = 256;     // 4 accumulator slots per lane
@@ -127,9 +129,8 @@ const char* last_pass_kernel();
 
 struct PosedModel {
   void* planes_w = nullptr;   // T
-  float* spheres_w = nullptr;
+  void* hull_rows = nullptr;  // [K+1] HullRow (pose_impl.h)
   void* verts_w = nullptr;    // T
-  void* hscale_w = nullptr;   // T
   float* screen_w = nullptr;  // [F+K][4] (f64 contexts; see the layout above)
   // f64 planes64 contexts: every hull's LDS stage image, [4F + K + 2V] 16-B
   // chunks; hull k at chunk 4·face_off[k] + k + 2·vert_off[k]: its screening

@@ -23,28 +23,17 @@ struct PassModel {
   const int32_t* __restrict__ rbf_row_off;   // [R+1] rows (n centres + 1 poly row)
   const int32_t* __restrict__ rbf_acc_off;   // [R+1] offsets in the RBF accumulator block
   const T* __restrict__ rbf_rows;            // [rows][4] (c, w) ... (a, b)
-  const int32_t* __restrict__ face_off;
-  const int32_t* __restrict__ vert_off;
   const I4* __restrict__ face_rows;          // [F] packed local vertex / neighbour indices
   const T* __restrict__ planes;
   const T* __restrict__ verts;
-  const T* __restrict__ hscale;
-  const float* __restrict__ spheres;
+  const I4* __restrict__ hull_rows;          // posed hull table, [K+1] HullRow (PosedModel::hull_rows)
   const float* __restrict__ screen;          // fp32 screening pairs (f64 contexts)
   const I4* __restrict__ image;              // per-hull stage images (planes64; PosedModel::image_w)
 };
 
-// Per-workgroup LDS hull table, filled once in the kernel prologue (row K is
-// a sentinel holding face_off[K] / vert_off[K]): the per-lane culling loops and
-// every hull evaluation read it at LDS latency instead of a global round trip.
-typedef float F4 __attribute__((ext_vector_type(4)));
-struct HullRow {
-  F4 sphere;      // world centroid + radius (f32, exact-safe culling)
-  F4 box[4];      // world oriented box: (centre, 0), 3 x (body axis, half extent)
-  int f0, v0;     // first face / vertex of the hull
-  double hscale;  // certificate scale max_v |v|_1
-};
-static_assert(sizeof(HullRow) == 96, "HullRow is 96 bytes");
+// Per-workgroup LDS hull table (HullRow: pose_impl.h), a copy of the posed
+// table made once in the kernel prologue: the per-lane culling loops and every
+// hull evaluation read it at LDS latency instead of a global round trip.
 
 // Lower bound of hull k's signed distance at x from its oriented box (the hull
 // lies inside the box): with u_i = |a_i·(x − c)| − e_i, outside the box
@@ -99,30 +88,16 @@ struct WaveSphere {
   float x, y, z, r;
 };
 
-// fill the table (whole workgroup; ends with a barrier) and return the
-// culling-margin scale smax = max_k |c_k|_1 + 2 r_k (wave-uniform)
+// copy the posed table (whole workgroup: its (K+1) x 6 16-byte chunks; ends
+// with a barrier) and return the culling-margin scale smax = max_k |c_k|_1 +
+// 2 r_k, which the pose left in the sentinel row (wave-uniform)
 template <typename T>
 __device__ __forceinline__ float load_hull_table(const PassModel<T>& m, HullRow* __restrict__ ht) {
-  for (int k = threadIdx.x; k <= m.K; k += (int)blockDim.x) {
-    HullRow r;
-    const F4* b = (const F4*)(m.spheres + kBoundFloats * k);  // row K (sentinel) is not read
-    r.sphere = k < m.K ? b[0] : F4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r.box[i] = k < m.K ? b[1 + i] : F4{0.f, 0.f, 0.f, 0.f};
-    r.f0 = m.face_off[k];
-    r.v0 = m.vert_off[k];
-    r.hscale = k < m.K ? (double)m.hscale[k] : 0.0;
-    ht[k] = r;
-  }
+  I4* dst = (I4*)ht;
+  const int nchunks = (m.K + 1) * (int)(sizeof(HullRow) / sizeof(I4));
+  for (int c = threadIdx.x; c < nchunks; c += (int)blockDim.x) dst[c] = m.hull_rows[c];
   __syncthreads();
-  float smax = 0.f;
-  for (int k = threadIdx.x & 63; k < m.K; k += 64) {
-    const F4 sp = ht[k].sphere;
-    smax = fmaxf(smax, fabsf(sp[0]) + fabsf(sp[1]) + fabsf(sp[2]) + 2.0f * sp[3]);
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) smax = fmaxf(smax, __shfl_xor(smax, off, 64));
-  return smax;
+  return ht[m.K].box[0][3];  // (one LDS read per lane, the same address)
 }
 
 // One bulk copy of everything hull k's evaluation reads — plane rows, vertex

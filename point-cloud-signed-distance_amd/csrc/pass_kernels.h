@@ -61,7 +61,7 @@ __global__ __launch_bounds__(NB) __attribute__((
   // more than 64 hulls (!CULL, !RBF, SLOTS > 1), which took 2 more and
   // therefore keep the lane value. When this line or scene_eval changes,
   // re-check the VGPRs / ScratchSize / Occupancy lines of every pass_kernel
-  // variant (profiles/r07/seed_first/resource_usage_head.txt is the record).
+  // variant (profiles/r09/pass_overhead/resource_usage_head.txt is the record).
   const int wave = (SLOTS == 1 || CULL || RBF) ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)
                                                 : (int)(threadIdx.x >> 6);
   // (wave-uniform: readfirstlane keeps the hull mask and the loops scalar)
@@ -179,12 +179,10 @@ __global__ __launch_bounds__(NB) __attribute__((
     // was spilled to scratch at the register budget)
     double cost_chunk = 0.0;
     if (!HPART || part == 0)  // (HPART: part 0 emits the chunk; the other waves' rows stay zero)
-      emit_chunk<T, SLOTS, RBF>(px, py, pz, valid, best, bk, gx, gy, gz, i, base, n, m, out, acc_row,
-                                ALIAS ? cost_chunk : cost_acc, rbf_wave, tstage, stage_cap);
-    if (ALIAS) {
-      cost_chunk = wave_sum(cost_chunk);
-      if (lane == 0) red_of(wave)[SLOTS * 64 * 6] = cost_chunk;
-    }
+      emit_chunk<T, SLOTS, RBF, ALIAS>(px, py, pz, valid, best, bk, gx, gy, gz, i, base, n, m, out, acc_row,
+                                       ALIAS ? cost_chunk : cost_acc, rbf_wave, tstage, stage_cap);
+    // (ALIAS: emit_chunk returned the chunk's sum)
+    if (ALIAS && lane == 0) red_of(wave)[SLOTS * 64 * 6] = cost_chunk;
 #if FSDF_WAVE_TIMES
     // diagnostic: 100 MHz wall clock around each wave-iteration of the first
     // grid pass (stats + 32 + 2 * wave), written by lane 0
@@ -282,10 +280,9 @@ __device__ __forceinline__ void emit_chunk_row(T px, T py, T pz, bool valid, T b
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   T* tstage = (T*)((char*)stage + (64 * 6 + 2) * 8);  // gradient transpose after the rows
   double cost_chunk = 0.0;
-  const uint64_t touched = emit_chunk<T, 1, false>(px, py, pz, valid, best, bk, gx, gy, gz, i, base, n, m, out,
-                                                   acc_row, cost_chunk, nullptr, tstage,
-                                                   m.stage_bytes / (4 * (int)sizeof(T)));
-  cost_chunk = wave_sum(cost_chunk);
+  const uint64_t touched = emit_chunk<T, 1, false, true>(px, py, pz, valid, best, bk, gx, gy, gz, i, base, n, m, out,
+                                                         acc_row, cost_chunk, nullptr, tstage,
+                                                         m.stage_bytes / (4 * (int)sizeof(T)));  // (cost_chunk: the chunk's sum)
   const int cnt = __builtin_popcountll(touched);
   if (cnt <= 4) {
     if ((touched >> lane) & 1) {

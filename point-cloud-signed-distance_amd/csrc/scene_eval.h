@@ -363,9 +363,14 @@ __device__ __forceinline__ void scene_eval(T px, T py, T pz, bool valid, const P
 
 // Per-chunk epilogue (pass and merge kernels): this wave's contributions
 //   c += d^2;  F_k += 2 d g;  M_k += 2 d (p x g)   (RBF skins: adjoint sums)
-// segmented by k* (ballot loop + DPP wave sums) into the LDS rows owned by
-// lane k, then the per-point outputs. Whole wave active.
-template <typename T, int SLOTS, bool RBF>
+// segmented by k* (ballot loop; the group's six sums in one packed wave
+// reduction, wave_sum_packed, added into surface k's LDS row by the lanes that
+// hold them), then the per-point outputs. acc_row: this lane's row (row `lane`
+// of the wave's rows). CHUNK_COST: the chunk's Σ d² rides in the first group's
+// reduction as a seventh value and is RETURNED in cost_acc (wave-uniform, the
+// bits of wave_sum over the lanes' d²); otherwise cost_acc is the lane's
+// running sum. Whole wave active.
+template <typename T, int SLOTS, bool RBF, bool CHUNK_COST = false>
 __device__ __forceinline__ uint64_t emit_chunk(T px, T py, T pz, bool valid, T best, int bk, T gx, T gy, T gz, int64_t i,
                                            int64_t base, int64_t n, const PassModel<T>& m, const PassOutputs& out,
                                            double* __restrict__ acc_row, double& cost_acc,
@@ -373,11 +378,13 @@ __device__ __forceinline__ uint64_t emit_chunk(T px, T py, T pz, bool valid, T b
   const int lane = threadIdx.x & 63;
   // contributions: c += d^2; F_k += 2 d g; M_k += 2 d (p x g)
   double cF[3] = {0.0, 0.0, 0.0}, cM[3] = {0.0, 0.0, 0.0};
+  double ccost = 0.0;  // (CHUNK_COST) this lane's d², until the first group has summed it
   if (valid) {
     const double bd = (double)best;
     const double dgx = gx, dgy = gy, dgz = gz;
     const double dpx = px, dpy = py, dpz = pz;
-    cost_acc = __builtin_fma(bd, bd, cost_acc);
+    if constexpr (CHUNK_COST) ccost = __builtin_fma(bd, bd, 0.0);
+    else cost_acc = __builtin_fma(bd, bd, cost_acc);
     const double w = 2.0 * bd;
     cF[0] = w * dgx; cF[1] = w * dgy; cF[2] = w * dgz;
     cM[0] = w * __builtin_fma(dpy, dgz, -(dpz * dgy));
@@ -387,6 +394,8 @@ __device__ __forceinline__ uint64_t emit_chunk(T px, T py, T pz, bool valid, T b
   const uint64_t tw = wt_now();
   uint64_t pending = __ballot(valid);
   uint64_t touched = 0;  // surfaces (k & 63) of this chunk's points
+  if constexpr (CHUNK_COST) cost_acc = 0.0;
+  constexpr int kSums = CHUNK_COST ? 7 : 6;
   while (pending) {
     const int leader = __builtin_ctzll(pending);
     const int kk = __builtin_amdgcn_readfirstlane(__shfl(bk, leader, 64));
@@ -402,16 +411,27 @@ __device__ __forceinline__ uint64_t emit_chunk(T px, T py, T pz, bool valid, T b
                   rbf_wave + m.rbf_acc_off[r]);
       continue;
     }
-    double v[6];
+    double v[kSums];
 #pragma unroll
     for (int j = 0; j < 3; ++j) { v[j] = sel ? cF[j] : 0.0; v[3 + j] = sel ? cM[j] : 0.0; }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) v[j] = wave_sum(v[j]);
-    if (lane == (kk & 63)) {
-      double* r = acc_row + (kk >> 6) * 64 * 6;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) r[j] += v[j];
+    if constexpr (CHUNK_COST) v[6] = ccost;
+    const double u = wave_sum_packed<kSums>(v);
+    if constexpr (CHUNK_COST) {
+      if (touched == (1ull << (kk & 63)))  // the chunk's first group (wave-uniform)
+        cost_acc = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(u), packed_sum_lane(6)),
+                                    __builtin_amdgcn_readlane(__double2loint(u), packed_sum_lane(6)));
+      ccost = 0.0;
     }
+    // the lanes that hold sum pj (packed_sum_lane) add it into row kk, (kk - lane)
+    // rows from their own: one add per sum, as before. (The holders' mask and
+    // index come from an opaque copy of the lane, so that they are not hoisted
+    // and carried through the loop — or, in the grid-stride kernels, through
+    // the next scene evaluation: the register budget again, see scene_eval's
+    // note and DESIGN §7 "Pass overhead".)
+    int l = lane;
+    asm volatile("" : "+v"(l));
+    const int pj = (l & 3) + ((l >> 2) & 4);
+    if (((l & 0x2c) == 0x0c) & (pj < 6)) acc_row[(kk - lane) * 6 + pj] += u;
   }
 
   {

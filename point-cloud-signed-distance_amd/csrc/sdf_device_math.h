@@ -154,4 +154,66 @@ __device__ __forceinline__ double wave_sum(double v) {
                           __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 
+// The wave totals of N <= 8 doubles at once, each with wave_sum's addition
+// tree at lane 63 — pairs (2i, 2i+1), quads, eights, rows of 16, then
+// (row 3 + row 2) + (row 1 + row 0); IEEE addition commutes, so the tree's
+// shape alone fixes the bits — in about a quarter of the adds. A scan keeps 64
+// prefixes per value where one total is wanted; here a level that halves the
+// lanes a value needs lets two values share a register: lanes whose level bit
+// is clear keep a's partial sums, the others b's (packed_level). Pairs and
+// quads pack 8 values into 2 registers (quad_perm), eights and rows run on
+// those two (row_shr 4, 8: lanes 12..15 of each row hold four row totals),
+// v_permlane16_swap lays the two registers' odd and even rows side by side for
+// ONE add of both row pairs, v_permlane32_swap does the same for the halves.
+// Returns the packed totals: value j's is in lane packed_sum_lane(j) (and the
+// same lane + 32). Whole wave active.
+template <int CTRL>
+__device__ __forceinline__ double packed_level(double a, double b, bool hi) {
+  const double x = hi ? b : a, y = hi ? a : b;
+  return x + dpp_shifted<CTRL, 0xf>(y);
+}
+template <int CTRL>
+__device__ __forceinline__ double plain_level(double a) { return a + dpp_shifted<CTRL, 0xf>(a); }
+// a + b after the swap: rows (SWAP32: halves) (0, 1) of a and b side by side
+template <bool SWAP32>
+__device__ __forceinline__ double swapped_sum(double a, double b) {
+  unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
+  unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
+  if constexpr (SWAP32) {
+    const auto lo = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
+    alo = lo[0]; blo = lo[1]; ahi = hi[0]; bhi = hi[1];
+  } else {
+    const auto lo = __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
+    alo = lo[0]; blo = lo[1]; ahi = hi[0]; bhi = hi[1];
+  }
+  return __hiloint2double((int)ahi, (int)alo) + __hiloint2double((int)bhi, (int)blo);
+}
+__device__ __forceinline__ constexpr int packed_sum_lane(int j) { return 12 + (j & 3) + 16 * (j >> 2); }
+template <int N>
+__device__ __forceinline__ double wave_sum_packed(const double (&v)[N]) {
+  static_assert(N >= 1 && N <= 8, "two packed registers: at most 8 values");
+  int lane = lane_id();
+  asm volatile("" : "+v"(lane));  // (the level masks are made here, not carried by the caller's loop)
+  const bool b0 = lane & 1, b1 = lane & 2;
+  constexpr int NR = (N + 1) / 2, NS = (NR + 1) / 2;
+  double r[NR], s[NS];
+#pragma unroll
+  for (int a = 0; a < NR; ++a)  // pairs: quad_perm [1, 0, 3, 2]
+    r[a] = 2 * a + 1 < N ? packed_level<0xB1>(v[2 * a], v[2 * a + 1 < N ? 2 * a + 1 : 0], b0) : plain_level<0xB1>(v[2 * a]);
+#pragma unroll
+  for (int b = 0; b < NS; ++b)  // quads: quad_perm [2, 3, 0, 1]
+    s[b] = 2 * b + 1 < NR ? packed_level<0x4E>(r[2 * b], r[2 * b + 1 < NR ? 2 * b + 1 : 0], b1) : plain_level<0x4E>(r[2 * b]);
+#pragma unroll
+  for (int b = 0; b < NS; ++b) {
+    s[b] = plain_level<0x114>(s[b]);  // eights: row_shr:4
+    s[b] = plain_level<0x118>(s[b]);  // rows: row_shr:8
+  }
+  // rows of s[0] | s[1]: (0 1 2 3 | 0' 1' 2' 3') -> (0 0' 2 2' | 1 1' 3 3'), summed:
+  // row 0 + row 1 and row 2 + row 3 of s[0] in rows 0, 2, of s[1] in rows 1, 3
+  const double t = swapped_sum<false>(s[0], s[NS - 1]);
+  return swapped_sum<true>(t, t);  // (lower half, lower half) + (upper half, upper half)
+}
+
 }  // namespace fsdf

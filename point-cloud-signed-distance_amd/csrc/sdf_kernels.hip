@@ -56,10 +56,10 @@ namespace fsdf {
 // (pose_item, the pose's work items: pose_impl.h)
 template <typename T>
 __device__ __forceinline__ void pose_body(const LocalModel& lm, const double* __restrict__ poses,
-                                          T* __restrict__ planes_w, float* __restrict__ spheres_w,
-                                          T* __restrict__ verts_w, T* __restrict__ hscale_w,
-                                          float* __restrict__ screen_w, I4* __restrict__ image_w) {
-  pose_item<T>(lm, poses, planes_w, spheres_w, verts_w, hscale_w, screen_w, image_w,
+                                          T* __restrict__ planes_w, HullRow* __restrict__ hull_rows,
+                                          T* __restrict__ verts_w, float* __restrict__ screen_w,
+                                          I4* __restrict__ image_w) {
+  pose_item<T>(lm, poses, planes_w, hull_rows, verts_w, screen_w, image_w,
                (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
@@ -71,22 +71,20 @@ __device__ __forceinline__ void pose_body(const LocalModel& lm, const double* __
 // solver loop's passes after convergence, solver.hip)
 template <typename T>
 __global__ __launch_bounds__(kBlock) void pose_kernel(LocalModel lm, const double* __restrict__ poses,
-                                                      T* __restrict__ planes_w, float* __restrict__ spheres_w,
-                                                      T* __restrict__ verts_w, T* __restrict__ hscale_w,
-                                                      float* __restrict__ screen_w, I4* __restrict__ image_w,
-                                                      const int* __restrict__ skip) {
+                                                      T* __restrict__ planes_w, HullRow* __restrict__ hull_rows,
+                                                      T* __restrict__ verts_w, float* __restrict__ screen_w,
+                                                      I4* __restrict__ image_w, const int* __restrict__ skip) {
   if (skip && *skip) return;
-  pose_body<T>(lm, poses, planes_w, spheres_w, verts_w, hscale_w, screen_w, image_w);
+  pose_body<T>(lm, poses, planes_w, hull_rows, verts_w, screen_w, image_w);
 }
 template <typename T>
 __global__ __launch_bounds__(kBlock) void pose_kernel_args(LocalModel lm, PoseArgs pa, T* __restrict__ planes_w,
-                                                           float* __restrict__ spheres_w, T* __restrict__ verts_w,
-                                                           T* __restrict__ hscale_w, float* __restrict__ screen_w,
-                                                           I4* __restrict__ image_w) {
+                                                           HullRow* __restrict__ hull_rows, T* __restrict__ verts_w,
+                                                           float* __restrict__ screen_w, I4* __restrict__ image_w) {
   __shared__ double sp[12 * kPoseArgMax];
   for (int i = threadIdx.x; i < 12 * lm.S; i += kBlock) sp[i] = pa.v[i];
   __syncthreads();
-  pose_body<T>(lm, sp, planes_w, spheres_w, verts_w, hscale_w, screen_w, image_w);
+  pose_body<T>(lm, sp, planes_w, hull_rows, verts_w, screen_w, image_w);
 }
 
 // Per-chunk bounding spheres of a resident cloud (one wave per 64 points),
@@ -207,19 +205,19 @@ hipError_t launch_pose(int precision, const LocalModel& lm, const double* d_pose
     memcpy(pa.v, h_poses, (size_t)12 * lm.S * sizeof(double));
     if (precision == 64)
       hipLaunchKernelGGL(pose_kernel_args<double>, dim3(grid), dim3(kBlock), 0, s, lm, pa, (double*)pm.planes_w,
-                         pm.spheres_w, (double*)pm.verts_w, (double*)pm.hscale_w, pm.screen_w, (I4*)pm.image_w);
+                         (HullRow*)pm.hull_rows, (double*)pm.verts_w, pm.screen_w, (I4*)pm.image_w);
     else
       hipLaunchKernelGGL(pose_kernel_args<float>, dim3(grid), dim3(kBlock), 0, s, lm, pa, (float*)pm.planes_w,
-                         pm.spheres_w, (float*)pm.verts_w, (float*)pm.hscale_w, (float*)nullptr, (I4*)nullptr);
+                         (HullRow*)pm.hull_rows, (float*)pm.verts_w, (float*)nullptr, (I4*)nullptr);
     return hipGetLastError();
   }
   if (precision == 64) {
     hipLaunchKernelGGL(pose_kernel<double>, dim3(grid), dim3(kBlock), 0, s, lm, d_poses,
-                       (double*)pm.planes_w, pm.spheres_w, (double*)pm.verts_w, (double*)pm.hscale_w,
-                       pm.screen_w, (I4*)pm.image_w, skip);
+                       (double*)pm.planes_w, (HullRow*)pm.hull_rows, (double*)pm.verts_w, pm.screen_w,
+                       (I4*)pm.image_w, skip);
   } else {
     hipLaunchKernelGGL(pose_kernel<float>, dim3(grid), dim3(kBlock), 0, s, lm, d_poses, (float*)pm.planes_w,
-                       pm.spheres_w, (float*)pm.verts_w, (float*)pm.hscale_w, (float*)nullptr, (I4*)nullptr, skip);
+                       (HullRow*)pm.hull_rows, (float*)pm.verts_w, (float*)nullptr, (I4*)nullptr, skip);
   }
   return hipGetLastError();
 }
@@ -238,13 +236,10 @@ static PassModel<T> pass_model(const LocalModel& lm, const PosedModel& pm) {
   m.rbf_row_off = lm.rbf_row_off;
   m.rbf_acc_off = lm.rbf_acc_off;
   m.rbf_rows = (const T*)pm.rbf_rows;
-  m.face_off = lm.face_off;
-  m.vert_off = lm.vert_off;
   m.face_rows = (const I4*)lm.face_rows;
   m.planes = (const T*)pm.planes_w;
   m.verts = (const T*)pm.verts_w;
-  m.hscale = (const T*)pm.hscale_w;
-  m.spheres = pm.spheres_w;
+  m.hull_rows = (const I4*)pm.hull_rows;
   m.screen = pm.screen_w;
   m.image = (const I4*)pm.image_w;
   return m;

@@ -446,7 +446,7 @@ __device__ void pose_tail(const SolverTree& T, const Lds& L, const LocalModel& l
   __syncthreads();
   const int item = blockIdx.x * NT + tid;
   if (item < pose_items(lm))
-    pose_item<TP>(lm, L.P, (TP*)pm.planes_w, pm.spheres_w, (TP*)pm.verts_w, (TP*)pm.hscale_w,
+    pose_item<TP>(lm, L.P, (TP*)pm.planes_w, (HullRow*)pm.hull_rows, (TP*)pm.verts_w,
                   sizeof(TP) == 8 ? pm.screen_w : nullptr, sizeof(TP) == 8 ? (I4*)pm.image_w : nullptr, item);
 }
 
