@@ -541,6 +541,83 @@ int fsdf_set_point_weights(fsdf_ctx* ctx, const double* weights /* [n], caller o
 int fsdf_set_point_weights_device(fsdf_ctx* ctx, const double* d_weights /* [n], caller order */, int64_t n);
 int fsdf_get_point_weights(fsdf_ctx* ctx, double* out /* [n], resident order, or NULL */, int32_t* set_out);
 
+/* ---- depth frames ----------------------------------------------------------------
+ * What a depth camera delivers is an image: 2 to 8 bytes per pixel over rays
+ * that never change (the reference's DepthSensor holds rays[rows, cols], a
+ * frame is the distances along them, and raycast_points turns those into the
+ * cloud, row-major with the misses dropped: src/depthsensors.jl:99-113). Here
+ * the rays stay resident, a frame is the depth image plus the sensor's pose,
+ * and the device back-projects and compacts the valid pixels
+ * (csrc/depth.hip: a count, a scan and a scatter on the context stream — no
+ * atomics, no workgroup waiting on another: the output order is a function of
+ * the image alone, bit-identical from run to run) and hands the fp64 cloud to
+ * the path of fsdf_set_points_device. The host link carries the image instead
+ * of 24 bytes per point, and every resident point knows its pixel
+ * (fsdf_get_depth_pixels), which is what per-pixel confidences need
+ * (fsdf_set_point_weights takes the caller's order, the order of that list).
+ *
+ * fsdf_set_sensor: rays [rows*cols][3] in the camera frame, row-major (pixel
+ * row*cols + col) — a context setting like the loss: it survives cloud and
+ * model swaps. One direction u per pixel is computed on the host, once, and
+ * kept on the device as fp64:
+ *   FSDF_DEPTH_RANGE  the depth is the distance along the ray (the reference's
+ *                     model): u = r / sqrt((x·x + y·y) + z·z), each component
+ *                     divided;
+ *   FSDF_DEPTH_Z      the depth is the camera-frame z (what real cameras
+ *                     report): u = (x / z, y / z, 1.0).
+ * A ray that is not finite or has no length, FSDF_DEPTH_Z with z <= 0, rows or
+ * cols < 1, rows·cols >= 2^31 or an unknown kind is FSDF_ERR_ARG and the earlier
+ * sensor stays. rays == NULL clears the sensor (rows, cols, kind ignored).
+ * fsdf_get_sensor: the sensor's shape and kind (rows 0: none); any output may
+ * be NULL.
+ *
+ * fsdf_set_depth_f64 / _f32 / _u16: a host image [rows*cols] of the sensor's
+ * shape becomes the resident cloud. pose: the project's 12 doubles (R
+ * row-major, then t) of the sensor in the world, NULL = identity. range:
+ * {near, far, scale}, NULL = {0, +inf, 1}. Per pixel i, in this operation
+ * order and uncontracted:
+ *   s = scale · (double)depth_i     (the widening is exact for all three formats)
+ *   valid iff s is finite, s > 0, s >= near and s <= far
+ *   c = (s·u_x, s·u_y, s·u_z)
+ *   p_j = ((R_j0·c_x + R_j1·c_y) + R_j2·c_z) + t_j
+ * The resident cloud is the valid pixels' points in row-major pixel order: the
+ * order of raycast_points, and the CALLER ORDER of this cloud (per-point
+ * outputs, fsdf_get_permutation, fsdf_set_point_weights).
+ * flash/depthsensors.py depth_points restates the arithmetic operation for
+ * operation: the same bits. From there the frame is exactly
+ * fsdf_set_points_device of that fp64 array — the Hilbert sort and
+ * permutation with sort_points, the fp32 conversion of fp32 contexts, the chunk
+ * spheres, the seeds carried from the previous cloud, cleared point weights, a
+ * pending auto regroup — by calling that path. Synchronous like
+ * fsdf_set_points: the image may be reused on return. No sensor:
+ * FSDF_ERR_STATE. A pose entry that is not finite, a NaN near or far,
+ * near > far, or a scale that is not finite and > 0: FSDF_ERR_ARG; in all of
+ * these the resident cloud stays. A frame with no valid pixel makes a cloud of
+ * 0 points resident: not an error (a pass over it costs 0).
+ * fsdf_set_depth_device: the same from an image in device memory (format
+ * FSDF_DEPTH_F64 / _F32 / _U16): only the upload is skipped.
+ *
+ * fsdf_get_depth_pixels: pixels_out[i] = row·cols + col of caller point i, *n_out
+ * the cloud's size; pixels_out may be NULL to read n alone. FSDF_ERR_STATE when
+ * the resident cloud did not come from a depth frame (every fsdf_set_points*
+ * ends a depth frame's list). Synchronous.
+ *
+ * Not done: a prefetched depth frame (fsdf_prefetch_points has no depth form: a
+ * live sensor has no next frame); ranged and keyed (sharded) depth frames;
+ * weights computed on the device (the caller forms them from the pixel list);
+ * a free-space term for the pixels that saw nothing. */
+enum { FSDF_DEPTH_RANGE = 0, FSDF_DEPTH_Z = 1 };
+int fsdf_set_sensor(fsdf_ctx* ctx, const double* rays /* [rows*cols][3], camera frame, row-major, or NULL */,
+                    int32_t rows, int32_t cols, int32_t depth_kind);
+int fsdf_get_sensor(const fsdf_ctx* ctx, int32_t* rows_out, int32_t* cols_out, int32_t* kind_out);
+int fsdf_set_depth_f64(fsdf_ctx* ctx, const double* depth, const double* pose /* [12] or NULL */,
+                       const double* range /* [3] or NULL */);
+int fsdf_set_depth_f32(fsdf_ctx* ctx, const float* depth, const double* pose, const double* range);
+int fsdf_set_depth_u16(fsdf_ctx* ctx, const uint16_t* depth, const double* pose, const double* range);
+enum { FSDF_DEPTH_F64 = 0, FSDF_DEPTH_F32 = 1, FSDF_DEPTH_U16 = 2 };
+int fsdf_set_depth_device(fsdf_ctx* ctx, const void* d_depth, int32_t format, const double* pose, const double* range);
+int fsdf_get_depth_pixels(fsdf_ctx* ctx, int32_t* pixels_out /* [n], caller order, or NULL */, int64_t* n_out);
+
 /* ---- Gauss-Newton for RBF skins: device side -----------------------------------
  * The skins' second moments M_r above, reduced on the device
  * (csrc/skin_moments.hip): a launch of its own after the pass — the pass

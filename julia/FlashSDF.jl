@@ -150,6 +150,45 @@ function set_points_prefetched!(ctx::Context)
     ctx.prefetched = nothing
 end
 
+"""
+The depth sensor's rays (src/depthsensors.jl DepthSensor: `rays[rows, cols]`, camera frame), kept
+on the device as one direction per pixel (fsdf_set_sensor). `z_depth = false`: a frame's depths
+are distances along the rays, the reference's model; `true`: camera-frame z. The C side reads the
+rays row-major, so the column-major matrix is transposed here.
+"""
+function set_sensor!{T}(ctx::Context, rays::AbstractMatrix{SVector{3, T}}; z_depth::Bool=false)
+    rows, cols = size(rays)
+    R = convert(Vector{SVector{3, Float64}}, vec(permutedims(rays, (2, 1))))
+    check(ctx.ptr, ccall((:fsdf_set_sensor, lib), Cint, (Ptr{Void}, Ptr{Float64}, Int32, Int32, Int32),
+                         ctx.ptr, reinterpret(Float64, R), Int32(rows), Int32(cols), Int32(z_depth ? 1 : 0)), "set_sensor")
+end
+
+"""
+One depth frame in place of raycast_points + set_points! (src/depthsensors.jl:99-113): `depths[rows, cols]`
+over the sensor's rays and the sensor's pose (R [3, 3], t [3]) in the world; the device back-projects
+the pixels with near <= scale * depth <= far (finite, > 0) and compacts them in row-major order
+(fsdf_set_depth_f64). `depth_pixels` names each resident point's pixel.
+"""
+function set_depth!(ctx::Context, depths::AbstractMatrix{Float64}, R::AbstractMatrix, t::AbstractVector;
+                    near::Float64=0.0, far::Float64=Inf, scale::Float64=1.0)
+    D = convert(Vector{Float64}, vec(permutedims(depths, (2, 1))))
+    pose = convert(Vector{Float64}, vcat(vec(permutedims(R, (2, 1))), t))
+    range = Float64[near, far, scale]
+    check(ctx.ptr, ccall((:fsdf_set_depth_f64, lib), Cint, (Ptr{Void}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.ptr, D, pose, range), "set_depth")
+end
+
+"The 1-based (row, col) of every point of the resident depth frame, in the points' order (fsdf_get_depth_pixels)."
+function depth_pixels(ctx::Context, cols::Integer)
+    n = Ref{Int64}(0)
+    check(ctx.ptr, ccall((:fsdf_get_depth_pixels, lib), Cint, (Ptr{Void}, Ptr{Int32}, Ref{Int64}),
+                         ctx.ptr, C_NULL, n), "get_depth_pixels")
+    pix = zeros(Int32, n[])
+    check(ctx.ptr, ccall((:fsdf_get_depth_pixels, lib), Cint, (Ptr{Void}, Ptr{Int32}, Ref{Int64}),
+                         ctx.ptr, pix, n), "get_depth_pixels")
+    [(div(p, cols) + 1, rem(p, cols) + 1) for p in pix]
+end
+
 "One GPU's shard of the frame's cloud (the cost is a sum over points,
 src/gradientdescent.jl:32): the whole cloud is Hilbert-sorted on the device and
 this context keeps the contiguous range [first, last] (1-based, inclusive) of

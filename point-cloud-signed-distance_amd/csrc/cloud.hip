@@ -1,6 +1,7 @@
 // cloud.hip — the resident cloud of a context: ingest (host, device, ranges,
-// keyed shards), the seeds carried from one cloud to the next, the next
-// frame's prefetch, and the regroup by nearest surface.
+// keyed shards, depth frames over a resident sensor), the seeds carried from
+// one cloud to the next, the next frame's prefetch, and the regroup by nearest
+// surface.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -89,6 +90,7 @@ static int set_points_impl(fsdf_ctx* c, const double* src, int64_t n, bool devic
   if (rc0) return rc0;
   c->n = 0;
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
+  c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
   const double* d_src = src;
   if (!device_src && n > 0) {
     HIPCHECK(c, c->staging.reserve((size_t)n * 3));
@@ -243,6 +245,7 @@ extern "C" int fsdf_set_points_keyed_device(fsdf_ctx* c, const double* d_xyz, co
   HIPCHECK(c, hipStreamSynchronize(c->stream));
   c->n = 0;
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
+  c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
   HIPCHECK(c, c->cur.pts.reserve((size_t)std::max<int64_t>(n, 1) * 3 * point_bytes(c)));
   HIPCHECK(c, c->cur.perm.reserve((size_t)std::max<int64_t>(n, 1)));
   if (n > 0) {
@@ -259,6 +262,161 @@ extern "C" int fsdf_set_points(fsdf_ctx* c, const double* xyz, int64_t n) {
 
 extern "C" int fsdf_set_points_device(fsdf_ctx* c, const double* d_xyz, int64_t n) {
   return set_points_impl(c, d_xyz, n, true, 0, n);
+}
+
+// ---- depth frames (include/flashsdf.h "depth frames"; kernels: depth.hip) ------
+// The sensor: one direction per pixel, computed here once and kept on the device.
+extern "C" int fsdf_set_sensor(fsdf_ctx* c, const double* rays, int32_t rows, int32_t cols, int32_t depth_kind) {
+  if (!c) return FSDF_ERR_ARG;
+  if (!rays) {  // clear
+    c->sensor_rows = c->sensor_cols = 0;
+    return FSDF_OK;
+  }
+  if (depth_kind != FSDF_DEPTH_RANGE && depth_kind != FSDF_DEPTH_Z)
+    return fail(c, FSDF_ERR_ARG, "set_sensor: unknown depth kind %d; the earlier sensor stays", depth_kind);
+  if (rows < 1 || cols < 1 || (int64_t)rows * cols > INT32_MAX)
+    return fail(c, FSDF_ERR_ARG, "set_sensor: %d x %d pixels (rows, cols >= 1, rows * cols < 2^31); the earlier sensor stays",
+                rows, cols);
+  const int64_t npix = (int64_t)rows * cols;
+  std::vector<double> u((size_t)npix * 3);
+  for (int64_t i = 0; i < npix; ++i) {
+    const double x = rays[3 * i], y = rays[3 * i + 1], z = rays[3 * i + 2];
+    bool ok = std::isfinite(x) && std::isfinite(y) && std::isfinite(z);
+    if (ok && depth_kind == FSDF_DEPTH_RANGE) {
+      const double nrm = sqrt((x * x + y * y) + z * z);
+      ok = std::isfinite(nrm) && nrm > 0.0;
+      if (ok) {
+        u[3 * i] = x / nrm;
+        u[3 * i + 1] = y / nrm;
+        u[3 * i + 2] = z / nrm;
+      }
+    } else if (ok) {
+      ok = z > 0.0;
+      if (ok) {
+        u[3 * i] = x / z;
+        u[3 * i + 1] = y / z;
+        u[3 * i + 2] = 1.0;
+      }
+    }
+    if (!ok)
+      return fail(c, FSDF_ERR_ARG,
+                  "set_sensor: ray %lld is (%g, %g, %g) (rays are finite and not zero, z > 0 for FSDF_DEPTH_Z); the "
+                  "earlier sensor stays", (long long)i, x, y, z);
+  }
+  HIPCHECK(c, hipSetDevice(c->device));
+  // (a depth frame still queued may read the table a growing reserve frees)
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  c->sensor_rows = c->sensor_cols = 0;
+  HIPCHECK(c, c->sensor_u.reserve(u.size()));
+  HIPCHECK(c, hipMemcpyAsync(c->sensor_u.get(), u.data(), u.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));  // (u is a host temporary)
+  c->sensor_rows = rows;
+  c->sensor_cols = cols;
+  c->sensor_kind = depth_kind;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_get_sensor(const fsdf_ctx* c, int32_t* rows_out, int32_t* cols_out, int32_t* kind_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (rows_out) *rows_out = c->sensor_rows;
+  if (cols_out) *cols_out = c->sensor_cols;
+  if (kind_out) *kind_out = c->sensor_kind;
+  return FSDF_OK;
+}
+
+// A frame: count and scan, the 8-byte total back (the one synchronisation that
+// sizes the cloud), the scatter into `staging`, and from there the frame is
+// fsdf_set_points_device of that array.
+static int set_depth_impl(fsdf_ctx* c, const void* depth, int format, bool device_src, const double* pose,
+                          const double* range, const char* who) {
+  if (!c) return FSDF_ERR_ARG;
+  if (format != FSDF_DEPTH_F64 && format != FSDF_DEPTH_F32 && format != FSDF_DEPTH_U16)
+    return fail(c, FSDF_ERR_ARG, "%s: unknown depth format %d", who, format);
+  if (c->sensor_rows < 1) return fail(c, FSDF_ERR_STATE, "%s: no sensor (fsdf_set_sensor first)", who);
+  if (!depth) return fail(c, FSDF_ERR_ARG, "%s: null depth image", who);
+  fsdf::DepthPose P = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, {0.0, 0.0, 0.0}};
+  if (pose) {
+    for (int j = 0; j < 12; ++j)
+      if (!std::isfinite(pose[j])) return fail(c, FSDF_ERR_ARG, "%s: pose entry %d is %g; the resident cloud stays", who, j, pose[j]);
+    for (int j = 0; j < 9; ++j) P.R[j] = pose[j];
+    for (int j = 0; j < 3; ++j) P.t[j] = pose[9 + j];
+  }
+  fsdf::DepthRange r = {0.0, HUGE_VAL, 1.0};
+  if (range) {
+    r.near = range[0];
+    r.far = range[1];
+    r.scale = range[2];
+    if (std::isnan(r.near) || std::isnan(r.far) || r.near > r.far)
+      return fail(c, FSDF_ERR_ARG, "%s: range [%g, %g] (near <= far, neither a NaN); the resident cloud stays", who,
+                  r.near, r.far);
+    if (!(std::isfinite(r.scale) && r.scale > 0.0))
+      return fail(c, FSDF_ERR_ARG, "%s: scale %g (finite and > 0); the resident cloud stays", who, r.scale);
+  }
+  const int64_t npix = (int64_t)c->sensor_rows * c->sensor_cols;
+  const size_t nblocks = (size_t)((npix + 255) / 256);
+  HIPCHECK(c, hipSetDevice(c->device));
+  // the previous frame's work may still read the staging buffer and the buffers a reserve frees
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  HIPCHECK(c, c->depth_counts.reserve(nblocks));
+  HIPCHECK(c, c->depth_total.reserve(1));
+  HIPCHECK(c, c->h_depth_total.reserve(1));
+  const void* d_depth = depth;
+  if (!device_src) {
+    const size_t bytes = (size_t)npix * fsdf::depth_format_bytes(format);
+    HIPCHECK(c, c->depth_raw.reserve(bytes));
+    HIPCHECK(c, hipMemcpyAsync(c->depth_raw.get(), depth, bytes, hipMemcpyHostToDevice, c->stream));
+    d_depth = c->depth_raw.get();
+  }
+  hipError_t e = fsdf::launch_depth_count(format, d_depth, npix, r, c->depth_counts.get(), c->depth_total.get(), c->stream);
+  if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "%s (count): %s", who, hipGetErrorString(e));
+  HIPCHECK(c, hipMemcpyAsync(c->h_depth_total.get(), c->depth_total.get(), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  const int64_t n = *c->h_depth_total.get();
+  if (n < 0 || n > npix) return fail(c, FSDF_ERR_HIP, "%s: %lld valid pixels of %lld", who, (long long)n, (long long)npix);
+  // (the resident cloud's pixel list is overwritten from here on: whatever
+  // happens next, it no longer names a depth frame's pixels)
+  c->depth_cloud = false;
+  HIPCHECK(c, c->staging.reserve((size_t)std::max<int64_t>(n, 1) * 3));
+  HIPCHECK(c, c->depth_pix.reserve((size_t)std::max<int64_t>(n, 1)));
+  if (n > 0) {
+    e = fsdf::launch_depth_scatter(format, d_depth, c->sensor_u.get(), npix, r, P, c->depth_counts.get(), c->staging.get(),
+                                   c->depth_pix.get(), c->stream);
+    if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "%s (scatter): %s", who, hipGetErrorString(e));
+  }
+  const int rc = set_points_impl(c, c->staging.get(), n, true, 0, n);
+  if (rc) return rc;
+  c->depth_cloud = true;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_depth_f64(fsdf_ctx* c, const double* depth, const double* pose, const double* range) {
+  return set_depth_impl(c, depth, FSDF_DEPTH_F64, false, pose, range, "set_depth_f64");
+}
+
+extern "C" int fsdf_set_depth_f32(fsdf_ctx* c, const float* depth, const double* pose, const double* range) {
+  return set_depth_impl(c, depth, FSDF_DEPTH_F32, false, pose, range, "set_depth_f32");
+}
+
+extern "C" int fsdf_set_depth_u16(fsdf_ctx* c, const uint16_t* depth, const double* pose, const double* range) {
+  return set_depth_impl(c, depth, FSDF_DEPTH_U16, false, pose, range, "set_depth_u16");
+}
+
+extern "C" int fsdf_set_depth_device(fsdf_ctx* c, const void* d_depth, int32_t format, const double* pose,
+                                     const double* range) {
+  return set_depth_impl(c, d_depth, format, true, pose, range, "set_depth_device");
+}
+
+extern "C" int fsdf_get_depth_pixels(fsdf_ctx* c, int32_t* pixels_out, int64_t* n_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (!c->depth_cloud)
+    return fail(c, FSDF_ERR_STATE, "get_depth_pixels: the resident cloud did not come from a depth frame");
+  if (n_out) *n_out = c->n;
+  if (!pixels_out || c->n == 0) return FSDF_OK;
+  HIPCHECK(c, hipSetDevice(c->device));
+  HIPCHECK(c, hipMemcpyAsync(pixels_out, c->depth_pix.get(), (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                             c->stream));
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  return FSDF_OK;
 }
 
 // The next frame's cloud ahead of time: its host-to-device copy runs on a
@@ -335,6 +493,7 @@ extern "C" int fsdf_set_points_prefetched(fsdf_ctx* c) {
   if (rc) return rc;
   c->n = 0;
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
+  c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
   std::swap(c->cur, c->next);
   return finish_resident(c, n, false, true);
 }

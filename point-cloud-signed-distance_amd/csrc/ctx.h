@@ -182,6 +182,19 @@ struct fsdf_ctx {
   // since, regather before the next robust launch). A cloud with no permutation reads conf_src.
   fsdf::DevBuf<double> conf_src, conf_res;
   bool conf_set = false, conf_stale = false;
+  // depth frames (fsdf_set_sensor, fsdf_set_depth_*; cloud.hip over depth.hip): the sensor — a
+  // context setting like the loss — as one direction per pixel, sensor_u [rows·cols][3]
+  // (sensor_rows == 0: none); the frame's raw image (host sources land here), the per-block
+  // counts / offsets, the pinned total; depth_pix [n] each caller point's pixel, valid while
+  // depth_cloud says the resident cloud came from a depth frame. The frame's fp64 cloud is
+  // written to `staging`.
+  int sensor_rows = 0, sensor_cols = 0, sensor_kind = 0;
+  fsdf::DevBuf<double> sensor_u;
+  fsdf::DevBuf<unsigned char> depth_raw;
+  fsdf::DevBuf<int32_t> depth_counts, depth_pix;
+  fsdf::DevBuf<int64_t> depth_total;
+  fsdf::PinnedBuf<int64_t> h_depth_total;
+  bool depth_cloud = false;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;

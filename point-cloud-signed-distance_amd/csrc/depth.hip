@@ -1,0 +1,156 @@
+// depth.hip — depth-frame ingest (include/flashsdf.h "depth frames"): a depth
+// image over the sensor's resident pixel directions becomes the fp64 cloud of
+// its valid pixels, in row-major pixel order, with each point's pixel index.
+//
+// Three launches on one stream, no atomics, and no workgroup waits on another
+// inside a launch — the output order is a function of the image alone:
+//   depth_count_kernel<T>    counts[block] = valid pixels of the block's 256
+//   depth_scan_kernel        counts -> exclusive prefix in place, total to a slot
+//   depth_scatter_kernel<T>  recomputes validity; a lane's slot = the block's
+//                            offset + the preceding waves' counts + the valid
+//                            lanes below it in its wave; writes xyz and pix
+// Per pixel, in this order and uncontracted (-ffp-contract=off):
+//   s = scale · (double)depth            (exact widening for f64, f32, u16)
+//   valid iff s finite, s > 0, near <= s <= far
+//   c = (s u_x, s u_y, s u_z)
+//   p_j = ((R_j0 c_x + R_j1 c_y) + R_j2 c_z) + t_j
+// flash/depthsensors.py depth_points restates it operation for operation.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "flashsdf.h"
+#include "fsdf_internal.h"
+
+namespace fsdf {
+
+constexpr int kDepthBlock = 256;   // one pixel per lane, four waves
+constexpr int kScanBlock = 1024;   // the scan's tile: one count per lane, sixteen waves
+
+template <typename T>
+__device__ __forceinline__ bool depth_valid(T raw, const DepthRange& r, double& s) {
+  s = r.scale * (double)raw;
+  return __builtin_isfinite(s) && s > 0.0 && s >= r.near && s <= r.far;  // (a NaN fails every comparison)
+}
+
+template <typename T>
+__global__ __launch_bounds__(kDepthBlock) void depth_count_kernel(const T* __restrict__ depth, int32_t npix,
+                                                                  DepthRange r, int32_t* __restrict__ counts) {
+  __shared__ int32_t wave_count[kDepthBlock / 64];
+  const int64_t i = (int64_t)blockIdx.x * kDepthBlock + threadIdx.x;
+  double s;
+  const bool v = i < npix && depth_valid(depth[i], r, s);
+  const unsigned long long m = __ballot(v);
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = __popcll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) counts[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+}
+
+// One workgroup: tiles of kScanBlock counts with a running carry. The counts
+// sum to < 2^31 (the image has fewer pixels): int32 throughout.
+__global__ __launch_bounds__(kScanBlock) void depth_scan_kernel(int32_t* __restrict__ counts, int32_t nblocks,
+                                                                int64_t* __restrict__ total_out) {
+  __shared__ int32_t wave_total[kScanBlock / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int32_t carry = 0;
+  for (int32_t base = 0; base < nblocks; base += kScanBlock) {
+    const int32_t i = base + (int32_t)threadIdx.x;
+    const int32_t v = i < nblocks ? counts[i] : 0;
+    int32_t x = v;  // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int32_t y = __shfl_up(x, o, 64);
+      if (lane >= o) x += y;
+    }
+    if (lane == 63) wave_total[w] = x;
+    __syncthreads();
+    int32_t before = 0, tile = 0;
+#pragma unroll
+    for (int k = 0; k < kScanBlock / 64; ++k) {
+      const int32_t t = wave_total[k];
+      if (k < w) before += t;
+      tile += t;
+    }
+    if (i < nblocks) counts[i] = carry + before + (x - v);
+    carry += tile;
+    __syncthreads();  // (the next tile rewrites wave_total)
+  }
+  if (threadIdx.x == 0) *total_out = carry;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kDepthBlock) void depth_scatter_kernel(const T* __restrict__ depth,
+                                                                    const double* __restrict__ u, int32_t npix,
+                                                                    DepthRange r, DepthPose P,
+                                                                    const int32_t* __restrict__ offsets,
+                                                                    double* __restrict__ xyz,
+                                                                    int32_t* __restrict__ pix) {
+  __shared__ int32_t wave_count[kDepthBlock / 64];
+  const int64_t i = (int64_t)blockIdx.x * kDepthBlock + threadIdx.x;
+  const int w = threadIdx.x >> 6;
+  double s = 0.0;
+  const bool v = i < npix && depth_valid(depth[i], r, s);
+  const unsigned long long m = __ballot(v);
+  if ((threadIdx.x & 63) == 0) wave_count[w] = __popcll(m);
+  __syncthreads();
+  if (!v) return;
+  int64_t slot = offsets[blockIdx.x];
+  for (int k = 0; k < w; ++k) slot += wave_count[k];
+  // the valid lanes below this one in its wave
+  slot += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  const double cx = s * u[3 * i + 0], cy = s * u[3 * i + 1], cz = s * u[3 * i + 2];
+  xyz[3 * slot + 0] = ((P.R[0] * cx + P.R[1] * cy) + P.R[2] * cz) + P.t[0];
+  xyz[3 * slot + 1] = ((P.R[3] * cx + P.R[4] * cy) + P.R[5] * cz) + P.t[1];
+  xyz[3 * slot + 2] = ((P.R[6] * cx + P.R[7] * cy) + P.R[8] * cz) + P.t[2];
+  pix[slot] = (int32_t)i;
+}
+
+static inline int depth_blocks(int64_t npix) { return (int)((npix + kDepthBlock - 1) / kDepthBlock); }
+
+template <typename T>
+static hipError_t count_scan(const void* d_depth, int64_t npix, const DepthRange& r, int32_t* d_counts,
+                             int64_t* d_total, hipStream_t s) {
+  const int nb = depth_blocks(npix);
+  hipLaunchKernelGGL(depth_count_kernel<T>, dim3((unsigned)nb), dim3(kDepthBlock), 0, s, (const T*)d_depth,
+                     (int32_t)npix, r, d_counts);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(depth_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, d_counts, (int32_t)nb, d_total);
+  return hipGetLastError();
+}
+
+static bool depth_args_ok(int format, const void* d_depth, int64_t npix) {
+  return d_depth && npix >= 1 && npix <= INT32_MAX &&
+         (format == FSDF_DEPTH_F64 || format == FSDF_DEPTH_F32 || format == FSDF_DEPTH_U16);
+}
+
+size_t depth_format_bytes(int format) {
+  return format == FSDF_DEPTH_F64 ? sizeof(double) : format == FSDF_DEPTH_F32 ? sizeof(float) : sizeof(uint16_t);
+}
+
+hipError_t launch_depth_count(int format, const void* d_depth, int64_t npix, const DepthRange& r, int32_t* d_counts,
+                              int64_t* d_total, hipStream_t s) {
+  if (!depth_args_ok(format, d_depth, npix) || !d_counts || !d_total) return hipErrorInvalidValue;
+  if (format == FSDF_DEPTH_F64) return count_scan<double>(d_depth, npix, r, d_counts, d_total, s);
+  if (format == FSDF_DEPTH_F32) return count_scan<float>(d_depth, npix, r, d_counts, d_total, s);
+  return count_scan<uint16_t>(d_depth, npix, r, d_counts, d_total, s);
+}
+
+template <typename T>
+static hipError_t scatter(const void* d_depth, const double* d_u, int64_t npix, const DepthRange& r,
+                          const DepthPose& P, const int32_t* d_offsets, double* d_xyz, int32_t* d_pix, hipStream_t s) {
+  hipLaunchKernelGGL(depth_scatter_kernel<T>, dim3((unsigned)depth_blocks(npix)), dim3(kDepthBlock), 0, s,
+                     (const T*)d_depth, d_u, (int32_t)npix, r, P, d_offsets, d_xyz, d_pix);
+  return hipGetLastError();
+}
+
+hipError_t launch_depth_scatter(int format, const void* d_depth, const double* d_u, int64_t npix, const DepthRange& r,
+                                const DepthPose& P, const int32_t* d_offsets, double* d_xyz, int32_t* d_pix,
+                                hipStream_t s) {
+  if (!depth_args_ok(format, d_depth, npix) || !d_u || !d_offsets || !d_xyz || !d_pix) return hipErrorInvalidValue;
+  if (format == FSDF_DEPTH_F64) return scatter<double>(d_depth, d_u, npix, r, P, d_offsets, d_xyz, d_pix, s);
+  if (format == FSDF_DEPTH_F32) return scatter<float>(d_depth, d_u, npix, r, P, d_offsets, d_xyz, d_pix, s);
+  return scatter<uint16_t>(d_depth, d_u, npix, r, P, d_offsets, d_xyz, d_pix, s);
+}
+
+}  // namespace fsdf

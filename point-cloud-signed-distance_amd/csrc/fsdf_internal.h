@@ -302,6 +302,27 @@ hipError_t launch_robust(int precision, bool moments, const void* d_pts, const i
 // into resident order; an index outside [0, n) reads as 0)
 hipError_t launch_gather_f64(const double* d_src, const int32_t* d_perm, int64_t n, double* d_res, hipStream_t s);
 
+// ---- depth-frame ingest (depth.hip) --------------------------------------------
+// A depth image of npix pixels (format FSDF_DEPTH_F64 / _F32 / _U16, device
+// memory) over the pixel directions d_u [npix][3] becomes the fp64 cloud of its
+// valid pixels in pixel order: s = scale · depth, valid iff finite, > 0 and in
+// [near, far]; p = R (s u) + t. launch_depth_count: the count per 256-pixel
+// block and their exclusive scan in place (d_counts [ceil(npix/256)]), the
+// total to *d_total — two launches. launch_depth_scatter, sized by that total:
+// d_xyz [total][3] and d_pix [total] (each point's pixel) — one launch.
+struct DepthRange {
+  double near, far, scale;
+};
+struct DepthPose {
+  double R[9], t[3];
+};
+size_t depth_format_bytes(int format);
+hipError_t launch_depth_count(int format, const void* d_depth, int64_t npix, const DepthRange& r, int32_t* d_counts,
+                              int64_t* d_total, hipStream_t s);
+hipError_t launch_depth_scatter(int format, const void* d_depth, const double* d_u, int64_t npix, const DepthRange& r,
+                                const DepthPose& P, const int32_t* d_offsets, double* d_xyz, int32_t* d_pix,
+                                hipStream_t s);
+
 // ---- second moments of RBF skins (skin_moments.hip) ----------------------------
 // Per skin r of n centres, m = 4n + 4: M_r [m][m] = Σ_{p: k*(p) = r's surface}
 // j(p) j(p)ᵀ, j the point's row in the layout of the skin's accumulator block

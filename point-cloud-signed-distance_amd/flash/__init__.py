@@ -15,7 +15,7 @@ from .robust import Huber, Tukey
 __all__ = ["BodyGeometry", "ConvexGeometry", "DeformableInterpolatingSkin", "InterpolatingGeometry",
            "Manipulator", "ManipulatorState", "RigidInterpolatingSkin", "SceneSkin", "hull_poses",
            "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError",
-           "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights"]
+           "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights", "DepthFrame"]
 
 
 def __getattr__(name):
@@ -32,6 +32,9 @@ def __getattr__(name):
     if name == "depth_noise_weights":  # per-point confidence weights from a depth sensor's axial noise
         from .depthsensors import depth_noise_weights
         return depth_noise_weights
+    if name == "DepthFrame":  # a depth image, its sensor and pose, taken wherever a sensed cloud is
+        from .depthsensors import DepthFrame
+        return DepthFrame
     if name == "DepthSensors":
         from . import depthsensors
         return depthsensors

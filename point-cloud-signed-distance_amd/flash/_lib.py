@@ -128,6 +128,13 @@ _PROTOS = {
     "fsdf_set_point_weights": (c_int32, [c_void_p, c_void_p, c_int64]),
     "fsdf_set_point_weights_device": (c_int32, [c_void_p, c_void_p, c_int64]),
     "fsdf_get_point_weights": (c_int32, [c_void_p, c_void_p, POINTER(c_int32)]),
+    "fsdf_set_sensor": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32]),
+    "fsdf_get_sensor": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "fsdf_set_depth_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsdf_set_depth_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsdf_set_depth_u16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fsdf_set_depth_device": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "fsdf_get_depth_pixels": (c_int32, [c_void_p, c_void_p, POINTER(c_int64)]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -520,6 +527,99 @@ class Context:
         out = np.empty(self.n, np.float64)
         check(self._lib.fsdf_get_point_weights(self._ctx, ptr(out), ctypes.byref(flag)), self._ctx,
               "get_point_weights")
+        return out
+
+    DEPTH_KINDS = {"range": 0, "z": 1}
+    DEPTH_FORMATS = {np.dtype(np.float64): ("fsdf_set_depth_f64", 0), np.dtype(np.float32): ("fsdf_set_depth_f32", 1),
+                     np.dtype(np.uint16): ("fsdf_set_depth_u16", 2)}
+
+    def set_sensor(self, rays, kind: str = "range"):
+        """fsdf_set_sensor: the depth sensor's rays [rows, cols, 3] (camera
+        frame), kept on the device as one direction per pixel — kind "range":
+        the depth is the distance along the ray (the reference's DepthSensor);
+        "z": the camera-frame z (u = (x/z, y/z, 1)). A context setting: cloud
+        and model swaps keep it. None clears it."""
+        self._sensor_of = None  # (whose sensor this is: CostFunctor records it after the call)
+        if rays is None:
+            check(self._lib.fsdf_set_sensor(self._ctx, None, 0, 0, 0), self._ctx, "set_sensor")
+            self.sensor_shape = None
+            return
+        if kind not in self.DEPTH_KINDS:
+            raise ValueError(f"set_sensor: kind must be 'range' or 'z', got {kind!r}")
+        r = np.ascontiguousarray(rays, np.float64)
+        if r.ndim != 3 or r.shape[2] != 3:
+            raise ValueError(f"set_sensor: rays must be [rows, cols, 3], got {r.shape}")
+        check(self._lib.fsdf_set_sensor(self._ctx, ptr(r), r.shape[0], r.shape[1], self.DEPTH_KINDS[kind]), self._ctx,
+              "set_sensor")
+        self.sensor_shape = r.shape[:2]
+
+    def sensor(self):
+        """fsdf_get_sensor: (rows, cols, kind) as the library holds them, or None."""
+        rows, cols, kind = c_int32(0), c_int32(0), c_int32(0)
+        check(self._lib.fsdf_get_sensor(self._ctx, ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(kind)),
+              self._ctx, "get_sensor")
+        return (rows.value, cols.value, ("range", "z")[kind.value]) if rows.value else None
+
+    @staticmethod
+    def _depth_args(pose, near, far, scale):
+        if pose is not None:
+            pose = pose.as_pose12() if hasattr(pose, "as_pose12") else pose
+            pose = np.ascontiguousarray(pose, np.float64).reshape(-1)
+            if pose.size != 12:
+                raise ValueError(f"set_depth: the pose is 12 doubles (R row-major, then t), got {pose.size}")
+        return pose, np.array([near, far, scale], np.float64)
+
+    def _num_points(self) -> int:
+        n = c_int64(0)
+        check(self._lib.fsdf_num_points(self._ctx, ctypes.byref(n)), self._ctx, "num_points")
+        return n.value
+
+    def set_depth(self, depth, pose=None, near: float = 0.0, far: float = float("inf"), scale: float = 1.0):
+        """fsdf_set_depth_f64 / _f32 / _u16 by the image's dtype: the depth
+        image [rows, cols] of the sensor (set_sensor) becomes the resident cloud
+        — the points R (s u) + t of the pixels with s = scale · depth finite,
+        > 0 and in [near, far], in row-major pixel order (depth_pixels() names
+        them); then as set_points. pose: the sensor in the world (a Transform
+        or 12 doubles; None: identity). Returns the number of points."""
+        d = np.asarray(depth)
+        if d.dtype not in self.DEPTH_FORMATS:
+            raise TypeError(f"set_depth: the image is float64, float32 or uint16, got {d.dtype}")
+        shape = getattr(self, "sensor_shape", None)
+        if shape is not None and d.size != shape[0] * shape[1]:
+            raise ValueError(f"set_depth: an image of {d.size} pixels for a sensor of {shape[0]} x {shape[1]}")
+        d = np.ascontiguousarray(d)
+        p, r = self._depth_args(pose, near, far, scale)
+        check(getattr(self._lib, self.DEPTH_FORMATS[d.dtype][0])(self._ctx, ptr(d), ptr(p), ptr(r)), self._ctx,
+              "set_depth")
+        self.n = self._num_points()
+        return self.n
+
+    def set_depth_device(self, dev_ptr: int, fmt, pose=None, near: float = 0.0, far: float = float("inf"),
+                         scale: float = 1.0):
+        """fsdf_set_depth_device: set_depth from an image in device memory
+        (rows·cols elements of fmt: a dtype — float64, float32, uint16 — or the
+        library's 0 / 1 / 2); only the upload is skipped."""
+        if not isinstance(fmt, (int, np.integer)):
+            dt = np.dtype(fmt)
+            if dt not in self.DEPTH_FORMATS:
+                raise TypeError(f"set_depth_device: the image is float64, float32 or uint16, got {dt}")
+            fmt = self.DEPTH_FORMATS[dt][1]
+        p, r = self._depth_args(pose, near, far, scale)
+        check(self._lib.fsdf_set_depth_device(self._ctx, c_void_p(dev_ptr), int(fmt), ptr(p), ptr(r)), self._ctx,
+              "set_depth_device")
+        self.n = self._num_points()
+        return self.n
+
+    def depth_pixels(self) -> np.ndarray:
+        """fsdf_get_depth_pixels: pixel (row·cols + col) of every point of the
+        resident depth frame, in caller order — the order per-point outputs and
+        set_point_weights use: w_img.ravel()[ctx.depth_pixels()] are per-pixel
+        confidences as point weights."""
+        n = c_int64(0)
+        check(self._lib.fsdf_get_depth_pixels(self._ctx, None, ctypes.byref(n)), self._ctx, "get_depth_pixels")
+        out = np.empty(n.value, np.int32)
+        if n.value:
+            check(self._lib.fsdf_get_depth_pixels(self._ctx, ptr(out), ctypes.byref(n)), self._ctx, "get_depth_pixels")
         return out
 
     def eval_skin_moments(self, poses):

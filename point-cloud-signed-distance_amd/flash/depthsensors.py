@@ -10,6 +10,12 @@ The per-ray secant march runs in raycast_kernel (fsdf_raycast), one lane per
 ray, on the same scene SDF as the residual pass. LCMGL drawing (:36-52,
 :120-135) is out of scope.
 
+DepthFrame / depth_points (the reverse direction, a camera's frame coming in):
+the depth image over the sensor's fixed rays and the sensor pose, which the
+device back-projects and compacts itself (Context.set_sensor / set_depth,
+csrc/depth.hip) in the order and arithmetic of raycast_points (:99-113);
+depth_points is its numpy twin, bit for bit.
+
 depth_noise_weights (not in the reference): per-point confidence weights from
 a structured-light sensor's axial noise model, for estimate_state / Tracker /
 track (`weights=`).
@@ -65,6 +71,86 @@ def raycast_points(surface: SceneSkin, sensor: DepthSensor, tform: Transform) ->
 
 def raycast(state: ManipulatorState, sensor: DepthSensor, tform: Transform, device: int = 0) -> np.ndarray:
     return raycast_points(skin(state, device), sensor, tform)
+
+
+def pixel_directions(sensor_rays, kind: str = "range") -> np.ndarray:
+    """One direction u per pixel [rows·cols, 3] as fsdf_set_sensor forms it,
+    operation for operation: kind "range" u = r / sqrt((x·x + y·y) + z·z), each
+    component divided; "z" u = (x / z, y / z, 1.0)."""
+    r = np.asarray(sensor_rays, np.float64)
+    if r.ndim != 3 or r.shape[2] != 3:
+        raise ValueError(f"pixel_directions: rays must be [rows, cols, 3], got {r.shape}")
+    r = r.reshape(-1, 3)
+    x, y, z = r[:, 0], r[:, 1], r[:, 2]
+    if not np.all(np.isfinite(r)):
+        raise ValueError("pixel_directions: rays must be finite")
+    if kind == "range":
+        nrm = np.sqrt((x * x + y * y) + z * z)
+        if not np.all(np.isfinite(nrm) & (nrm > 0.0)):
+            raise ValueError("pixel_directions: a ray has no length")
+        return np.stack([x / nrm, y / nrm, z / nrm], axis=1)
+    if kind == "z":
+        if not np.all(z > 0.0):
+            raise ValueError("pixel_directions: kind 'z' needs rays with z > 0")
+        return np.stack([x / z, y / z, np.ones_like(z)], axis=1)
+    raise ValueError(f"pixel_directions: kind must be 'range' or 'z', got {kind!r}")
+
+
+def depth_points(depth, sensor_rays, tform: Transform | None, near: float = 0.0, far: float = np.inf,
+                 scale: float = 1.0, kind: str = "range"):
+    """The cloud of a depth image -> (points [n, 3], pixels [n]): the numpy twin
+    of fsdf_set_depth_* (csrc/depth.hip), the same bits. depth [rows, cols]
+    (float64, float32 or uint16) over sensor_rays [rows, cols, 3]; tform the
+    sensor in the world (None: identity). Per pixel, in this operation order
+    (explicit column arithmetic — a BLAS product may fuse or reorder):
+      s = scale · float64(depth); valid iff s finite, s > 0, near <= s <= far
+      c = (s u_x, s u_y, s u_z), u = pixel_directions(sensor_rays, kind)
+      p_j = ((R_j0 c_x + R_j1 c_y) + R_j2 c_z) + t_j
+    The valid pixels in row-major order (src/depthsensors.jl:99-113
+    raycast_points: misses dropped); pixels[i] = row · cols + col of point i."""
+    d = np.asarray(depth)
+    if d.dtype not in (np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.uint16)):
+        raise TypeError(f"depth_points: the image is float64, float32 or uint16, got {d.dtype}")
+    u = pixel_directions(sensor_rays, kind)
+    if d.size != len(u):
+        raise ValueError(f"depth_points: an image of {d.size} pixels over {len(u)} rays")
+    near, far, scale = np.float64(near), np.float64(far), np.float64(scale)
+    if np.isnan(near) or np.isnan(far) or near > far:
+        raise ValueError(f"depth_points: range [{near}, {far}] (near <= far, neither a NaN)")
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"depth_points: scale {scale} (finite and > 0)")
+    R = np.eye(3) if tform is None else np.asarray(tform.R, np.float64)
+    t = np.zeros(3) if tform is None else np.asarray(tform.t, np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = scale * d.reshape(-1).astype(np.float64)
+        valid = np.isfinite(s) & (s > 0.0) & (s >= near) & (s <= far)
+    pixels = np.flatnonzero(valid).astype(np.int32)
+    s = s[valid]
+    cx, cy, cz = s * u[valid, 0], s * u[valid, 1], s * u[valid, 2]
+    points = np.empty((len(s), 3), np.float64)
+    for j in range(3):
+        points[:, j] = ((R[j, 0] * cx + R[j, 1] * cy) + R[j, 2] * cz) + t[j]
+    return points, pixels
+
+
+@dataclass
+class DepthFrame:
+    """One frame of a depth camera as it arrives: the image over a DepthSensor's
+    fixed rays and the sensor's pose. estimate_state, Tracker.step, track and
+    CostFunctor take it wherever they take a cloud; the device then
+    back-projects and compacts it (Context.set_depth) and the host never forms
+    the points unless something asks for them (points())."""
+    depth: np.ndarray   # [rows, cols] float64, float32 or uint16
+    sensor: DepthSensor
+    tform: Transform | None = None  # the sensor in the world (None: identity)
+    near: float = 0.0
+    far: float = np.inf
+    scale: float = 1.0
+    kind: str = "range"
+
+    def points(self):
+        """(points [n, 3], pixels [n]) by depth_points: the resident cloud's bits."""
+        return depth_points(self.depth, self.sensor.rays, self.tform, self.near, self.far, self.scale, self.kind)
 
 
 def depth_noise_weights(points, origin, axis, sigma0: float = 0.0012, k: float = 0.0019, z0: float = 0.4):

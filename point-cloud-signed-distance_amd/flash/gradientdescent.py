@@ -15,6 +15,7 @@ from __future__ import annotations
 import numpy as np
 
 from .core import ConvexGeometry, InterpolatingGeometry, Manipulator, ManipulatorState, prepare_pass
+from .depthsensors import DepthFrame
 
 default_deformation_cost_weight = 10
 
@@ -110,17 +111,21 @@ class CostFunctor:
     """CostFunctor(manipulator, sensed_points) (src/gradientdescent.jl:41-57).
 
     The sensed cloud is uploaded once (the reference keeps it by reference for
-    every evaluation); each call ships only the hull poses."""
+    every evaluation); each call ships only the hull poses. sensed_points may
+    be a depthsensors.DepthFrame: the depth image is uploaded and the device
+    forms the cloud (Context.set_depth); `sensed_points` then forms the host
+    copy (frame.points()) only when it is read, `n_points` is the cloud's size
+    either way and `depth_pixels()` names each point's pixel."""
 
     def __init__(self, manipulator: Manipulator, sensed_points, device: int = 0, precision: int = 64,
                  deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False, loss=None):
         self.manipulator = manipulator
-        self.sensed_points = np.ascontiguousarray(sensed_points, np.float64).reshape(-1, 3)
         self.weight = deformation_cost_weight
         self.state = ManipulatorState(manipulator)
         self.ctx = manipulator.engine(device, precision)
         # a private context would be needed to keep two functors resident at once
-        self.ctx.set_points(self.sensed_points)
+        self._take(sensed_points)
+        self._upload()
         self._resident = id(self)
         manipulator._resident_cloud = self._resident
         # the whole iteration (FK, RBF weight solve, pass, chain rule,
@@ -147,6 +152,51 @@ class CostFunctor:
         # None: every point counts 1), dropped whenever the sensed points change
         self.point_weights = None
 
+    @property
+    def sensed_points(self):
+        """The sensed cloud [n, 3] on the host; of a DepthFrame, formed on the
+        first read (frame.points(): the resident cloud's bits and order)."""
+        if self._points is None:
+            self._points = self._frame.points()[0]
+        return self._points
+
+    @sensed_points.setter
+    def sensed_points(self, points):
+        self._frame, self._points = None, points
+
+    def _take(self, sensed_points):
+        # a DepthFrame as it is, anything else as the [n, 3] f64 array
+        if isinstance(sensed_points, DepthFrame):
+            self._frame, self._points = sensed_points, None
+        else:
+            self.sensed_points = np.ascontiguousarray(sensed_points, np.float64).reshape(-1, 3)
+
+    def _upload(self):
+        """Make this functor's cloud resident: set_points of the array, or — a
+        DepthFrame — set_depth of its image, after set_sensor when the
+        context's sensor is not the frame's already (by identity, like
+        _mechanism_of)."""
+        f = self._frame
+        if f is None:
+            self.ctx.set_points(self._points)
+        else:
+            have = getattr(self.ctx, "_sensor_of", None)
+            if have is None or have[0] is not f.sensor or have[1] != f.kind:
+                self.ctx._sensor_of = None
+                self.ctx.set_sensor(f.sensor.rays, f.kind)
+                self.ctx._sensor_of = (f.sensor, f.kind)
+            self.ctx.set_depth(f.depth, f.tform, f.near, f.far, f.scale)
+        self.n_points = self.ctx.n
+
+    def depth_pixels(self):
+        """Of a DepthFrame: pixel (row · cols + col) of every sensed point, in
+        the points' order (fsdf_get_depth_pixels) — per-pixel confidences
+        w_img.ravel()[cost.depth_pixels()] are point weights."""
+        if self._frame is None:
+            raise ValueError("depth_pixels: the sensed points did not come from a DepthFrame")
+        self._ensure_resident()
+        return self.ctx.depth_pixels()
+
     def set_point_weights(self, weights):
         """Per-point confidence weights a_i >= 0 of this functor's objective,
         one per sensed point in the order of `sensed_points` (None: none):
@@ -160,8 +210,8 @@ class CostFunctor:
                 raise NotImplementedError(
                     "point weights: they serve native rigid scenes (no RBF skin, no deformation)")
             weights = np.array(weights, np.float64, copy=True).reshape(-1)
-            if len(weights) != len(self.sensed_points):
-                raise ValueError(f"point weights: {len(weights)} weights for {len(self.sensed_points)} sensed points")
+            if len(weights) != self.n_points:
+                raise ValueError(f"point weights: {len(weights)} weights for {self.n_points} sensed points")
         self._ensure_resident()
         self.ctx.set_point_weights(weights)  # (refused: the earlier weights stay, here too)
         self.point_weights = weights
@@ -197,16 +247,18 @@ class CostFunctor:
     def set_sensed_points(self, sensed_points):
         """Swap the resident cloud (a new frame): one upload + device sort; the
         functor, its state and the device model are kept. The array given to
-        prefetch_sensed_points last is made resident from its device copy."""
+        prefetch_sensed_points last is made resident from its device copy. A
+        depthsensors.DepthFrame is made resident from its image (set_depth)."""
         pre, src = getattr(self, "_prefetched", None), getattr(self, "_prefetched_src", None)
         self._prefetched = self._prefetched_src = None
         self.point_weights = None  # (another cloud: the library drops its copy with the old one)
         if pre is not None and sensed_points is src:  # (the object prefetched: its device copy)
             self.sensed_points = pre
             self.ctx.set_points_prefetched()
+            self.n_points = self.ctx.n
         else:
-            self.sensed_points = np.ascontiguousarray(sensed_points, np.float64).reshape(-1, 3)
-            self.ctx.set_points(self.sensed_points)
+            self._take(sensed_points)
+            self._upload()
         self.manipulator._resident_cloud = self._resident
 
     def prefetch_sensed_points(self, sensed_points):
@@ -228,7 +280,7 @@ class CostFunctor:
 
     def _ensure_resident(self):
         if getattr(self.manipulator, "_resident_cloud", None) != self._resident:
-            self.ctx.set_points(self.sensed_points)
+            self._upload()
             self.manipulator._resident_cloud = self._resident
             if getattr(self, "point_weights", None) is not None:  # (they left with the cloud)
                 self.ctx.set_point_weights(self.point_weights)

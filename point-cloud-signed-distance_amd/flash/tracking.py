@@ -37,6 +37,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .core import Manipulator, ManipulatorState, num_states
+from .depthsensors import DepthFrame
 from .gradientdescent import CostFunctor, flatten, unflatten
 
 
@@ -195,11 +196,13 @@ def _default_solver(manipulator):
 
 def _frame_weights(weights, points):
     """weights as estimate_state / Tracker / track take them: None, one array
-    per call, or a callable points -> weights applied to the frame's cloud."""
+    per call, or a callable points -> weights applied to the frame's cloud
+    (points may itself be a callable -> points: a DepthFrame's host cloud is
+    formed only when a weights callable asks for it)."""
     if weights is None:
         return None
     if callable(weights):
-        weights = weights(points)
+        weights = weights(points() if callable(points) else points)
     return np.asarray(weights, np.float64).reshape(-1)
 
 
@@ -283,11 +286,20 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
     weights: one confidence weight >= 0 per sensed point (an array, or a
     callable points -> weights, e.g. depthsensors.depth_noise_weights bound to
     a sensor pose): the objective is Σ a ρ(d*) / N — native rigid scenes; set
-    after the cloud is resident."""
-    pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
+    after the cloud is resident.
+    sensed_points may be a depthsensors.DepthFrame (the depth image, the
+    sensor and its pose): the device forms the cloud (fsdf_set_depth_*), N is
+    the number of valid pixels, and the host forms the points only for a
+    weights callable."""
     solver = solver or _default_solver(manipulator)
-    cost = CostFunctor(manipulator, pts, device=device, precision=precision)
-    return _optimize(cost, len(pts), x_estimated, callback, solver, loss=loss, weights=_frame_weights(weights, pts))
+    if isinstance(sensed_points, DepthFrame):
+        cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision)
+        pts = lambda: cost.sensed_points  # noqa: E731 (formed when asked for)
+    else:
+        pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
+        cost = CostFunctor(manipulator, pts, device=device, precision=precision)
+    return _optimize(cost, cost.n_points, x_estimated, callback, solver, loss=loss,
+                     weights=_frame_weights(weights, pts))
 
 
 def notebook_frame_solver(manipulator):
@@ -322,15 +334,22 @@ class Tracker:
         under this frame's solver iterations (CostFunctor.prefetch_sensed_points).
         weights (optional): this frame's confidence weights, an array or a
         callable points -> weights; None: the Tracker's own. They are set after
-        the frame's cloud is resident, prefetched or not."""
-        pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
+        the frame's cloud is resident, prefetched or not.
+        sensed_points may be a depthsensors.DepthFrame: its image is made
+        resident by the device ingest (never prefetched), and the host forms
+        its points only for a weights callable."""
+        if isinstance(sensed_points, DepthFrame):
+            pts = lambda: self.cost.sensed_points  # noqa: E731 (formed when asked for)
+        else:
+            pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
         t0 = time.perf_counter()
         self.cost.set_sensed_points(sensed_points)  # (the object itself: a prefetched frame is matched by identity)
-        if next_points is not None:
+        if next_points is not None and not isinstance(next_points, DepthFrame):
             self.cost.prefetch_sensed_points(next_points)
         t1 = time.perf_counter()
         w = _frame_weights(self.weights if weights is None else weights, pts)
-        x = _optimize(self.cost, len(pts), flatten(self.state), callback, self.solver, loss=self.loss, weights=w)
+        x = _optimize(self.cost, self.cost.n_points, flatten(self.state), callback, self.solver, loss=self.loss,
+                      weights=w)
         unflatten(self.state, x)
         t2 = time.perf_counter()
         self.set_points_ms.append((t1 - t0) * 1e3)
@@ -348,7 +367,8 @@ def track(manipulator: Manipulator, frames, state: ManipulatorState | None = Non
           device: int = 0, precision: int = 64, loss=None, weights=None):
     """for event in log: gradient_descent!(state, model, sensed_points)
     (examples/irb_and_squishable.ipynb cells 11-12). `frames` yields sensed
-    clouds ([n,3]); returns (the per-frame solutions [F, n_states], the Tracker).
+    clouds ([n,3]) or depthsensors.DepthFrames (made resident by the device
+    ingest, not prefetched); returns (the per-frame solutions [F, n_states], the Tracker).
     loss: a robust point loss for every frame (flash.robust).
     weights: a callable points -> weights applied to every frame (or one array,
     where every frame has as many points)."""
