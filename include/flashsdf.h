@@ -756,8 +756,11 @@ int fsdf_set_points_keyed_device(fsdf_ctx* ctx, const double* d_xyz, const uint3
  * the planned pass is bound by its heaviest chunk, which grouping makes heavier
  * (DESIGN.md §7 round 5). The resident order changes: re-read
  * fsdf_get_permutation for FSDF_ORDER_RESIDENT outputs. Requires a sorted
- * (sort_points) or ranged cloud and a pass over it (hull-only scenes of <= 64
- * surfaces); asynchronous on the context stream. */
+ * (sort_points) or ranged cloud and a pass over that very cloud (hull-only
+ * scenes of <= 64 surfaces): FSDF_ERR_STATE, with the resident order unchanged,
+ * before the first pass since the cloud was set — also when that cloud's first
+ * pass will be seeded from the previous cloud (the carried seeds are hints, not
+ * this cloud's nearest surfaces). Asynchronous on the context stream. */
 int fsdf_regroup_points(fsdf_ctx* ctx);
 /* The regroup where it pays, decided by the library: only after a pass that
  * ran one wave per chunk (the grid above the planned window, bound by its

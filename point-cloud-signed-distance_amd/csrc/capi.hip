@@ -37,7 +37,7 @@ static void free_model(fsdf_ctx* c) {
   // (the partition tiers are a context setting: they survive a model change)
   const int64_t h4 = c->lm.hpart4_points, h2 = c->lm.hpart2_points;
   c->plan_nc = -1;
-  c->prior_ok = false;        // seeds name surfaces of the old model
+  c->prior_ok = c->prior_pass = false;  // seeds name surfaces of the old model
   c->solver_tree_ok = false;  // (its surface list)
   c->last_pass_shape = 0;
   c->lm = fsdf::LocalModel();

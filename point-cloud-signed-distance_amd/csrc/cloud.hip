@@ -59,7 +59,7 @@ static int ensure_vox_box(fsdf_ctx* c, const double* d_src, int64_t n) {
 
 static int carry_seeds_out(fsdf_ctx* c) {
   c->seed_pending = false;
-  if (!c->vox_ok || !seeds_apply(c) || c->n <= 0 || !c->prior_ok || c->prior.capacity() < (size_t)c->n || c->ranged)
+  if (!c->vox_ok || !seeds_apply(c) || c->n <= 0 || !c->prior_pass || c->prior.capacity() < (size_t)c->n || c->ranged)
     return FSDF_OK;
   uint8_t* grid = c->vox_grid.get();
   HIPCHECK(c, hipMemsetAsync(grid, 0xFF, (size_t)fsdf::kVoxDim * fsdf::kVoxDim * fsdf::kVoxDim, c->stream));
@@ -169,8 +169,9 @@ static int finish_resident(fsdf_ctx* c, int64_t n, bool ranged, bool spheres_don
     if (c->prior.capacity() < (size_t)n) HIPCHECK(c, hipStreamSynchronize(c->stream));
     HIPCHECK(c, c->prior.reserve((size_t)n));
   }
-  // a new cloud: its first pass seeds from the previous cloud's voxels, else from the bounds
-  c->prior_ok = false;
+  // a new cloud: its first pass seeds from the previous cloud's voxels, else from the bounds;
+  // gathered seeds are readable (prior_ok) but no pass's k* (prior_pass): 0xFF where no voxel was hit
+  c->prior_ok = c->prior_pass = false;
   if (c->seed_pending && n > 0 && !ranged) {
     hipError_t e = fsdf::vox_gather(c->precision, c->cur.pts.get(), n, c->vox, c->vox_grid.get(), c->prior.get(),
                                     c->stream);
@@ -518,7 +519,7 @@ extern "C" int fsdf_regroup_points(fsdf_ctx* c) {
   if (c->n == 0) return FSDF_OK;
   if (!c->cur.perm.get())
     return fail(c, FSDF_ERR_STATE, "regroup_points: needs a sorted (sort_points) or ranged resident cloud");
-  if (!c->prior_ok || c->prior.capacity() < (size_t)c->n)
+  if (!c->prior_pass || c->prior.capacity() < (size_t)c->n)
     return fail(c, FSDF_ERR_STATE, "regroup_points: run a pass over the resident cloud first (hull-only scenes)");
   HIPCHECK(c, hipSetDevice(c->device));
   hipError_t e =
@@ -545,7 +546,7 @@ extern "C" int fsdf_regroup_points(fsdf_ctx* c) {
 // 0.0612 -> 0.0677 ms and worse). Needs a pass over the
 // cloud (its k* are the groups) and a sorted or ranged cloud.
 static bool regroup_wanted(const fsdf_ctx* c) {
-  return c->n > 0 && c->cur.perm.get() && c->prior_ok && !c->regrouped && c->last_pass_shape == 1;
+  return c->n > 0 && c->cur.perm.get() && c->prior_pass && !c->regrouped && c->last_pass_shape == 1;
 }
 
 extern "C" int fsdf_regroup_auto(fsdf_ctx* c, int32_t* applied_out) {

@@ -100,7 +100,12 @@ struct fsdf_ctx {
   int64_t n = 0;
   ResidentCloud cur;
   fsdf::DevBuf<uint8_t> prior;       // [n] each resident point's nearest surface in the last pass (seed hint)
-  bool prior_ok = false;             // prior was written by a pass over the current resident cloud
+  bool prior_ok = false;             // prior is readable as seeds: every byte a surface of the model or 0xFF
+                                     // (none) — written by a pass over the resident cloud, or gathered from
+                                     // the previous cloud's voxels (finish_resident); the pass's prior_in
+  bool prior_pass = false;           // ... and a pass over the current resident cloud wrote every byte (each
+                                     // its point's k* < 64, never 0xFF): what the regroup groups by and the
+                                     // next cloud's seeds are carried from
   // regroup (fsdf_regroup_points): mode (fsdf_set_regroup), whether the
   // resident cloud has been regrouped since its set_points, whether its first
   // iteration pass is still to come (the auto regroup follows that pass), and

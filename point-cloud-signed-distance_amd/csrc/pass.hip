@@ -177,7 +177,7 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
   out.chunk_ws = resident ? c->cur.chunk_ws.get() : nullptr;  // resident cloud only
   // the previous pass's nearest surfaces as seeds (resident cloud, hull-only
   // scenes of <= 64 surfaces; fsdf_internal.h PassOutputs::prior_in); marked
-  // written (prior_ok) once the pass is launched — stream-ordered, the next
+  // written (prior_ok, prior_pass) once the pass is launched — stream-ordered, the next
   // pass reads what this one writes
   const bool prior = resident && n > 0 && c->prior.capacity() >= (size_t)n && c->lm.R == 0 && c->lm.S <= 64;
   out.prior_out = prior ? c->prior.get() : nullptr;
@@ -191,7 +191,7 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
     const fsdf::Event* pe = prof ? &c->prof_ev[c->prof_used] : nullptr;
     rc = run_planned(c, c->pm, d_pts, n, d_accum, out, pe, skip);
     if (rc) return rc;
-    if (prior) c->prior_ok = true;
+    if (prior) c->prior_ok = c->prior_pass = true;
     if (resident) c->last_pass_shape = 3;
     if (prof) c->prof_used += 3;
     return FSDF_OK;
@@ -212,7 +212,7 @@ static int run_pass_impl(fsdf_ctx* c, const double* poses, const void* d_pts, in
     HIPCHECK(c, fsdf::launch_pass(c->precision, c->cull != 0, c->lm, c->pm, d_pts, n, nblocks, out, c->stream,
                                   pe ? (hipEvent_t)pe[0] : nullptr, pe ? (hipEvent_t)pe[1] : nullptr));
     c->pass_kernel = fsdf::last_pass_kernel();
-    if (prior) c->prior_ok = true;
+    if (prior) c->prior_ok = c->prior_pass = true;
     if (resident) c->last_pass_shape = fsdf::hpart_pass(c->lm, n) ? 2 : 1;
     if (prof) c->prof_used += 3;
     // the order is rebuilt on the first scheduled pass of a grid and then every
