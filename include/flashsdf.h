@@ -604,8 +604,9 @@ int fsdf_get_point_weights(fsdf_ctx* ctx, double* out /* [n], resident order, or
  *
  * Not done: a prefetched depth frame (fsdf_prefetch_points has no depth form: a
  * live sensor has no next frame); ranged and keyed (sharded) depth frames;
- * weights computed on the device (the caller forms them from the pixel list);
- * a free-space term for the pixels that saw nothing. */
+ * weights computed on the device (the caller forms them from the pixel list).
+ * The free-space term for what the rays passed through and for the pixels that
+ * saw nothing: "free space" below. */
 enum { FSDF_DEPTH_RANGE = 0, FSDF_DEPTH_Z = 1 };
 int fsdf_set_sensor(fsdf_ctx* ctx, const double* rays /* [rows*cols][3], camera frame, row-major, or NULL */,
                     int32_t rows, int32_t cols, int32_t depth_kind);
@@ -617,6 +618,93 @@ int fsdf_set_depth_u16(fsdf_ctx* ctx, const uint16_t* depth, const double* pose,
 enum { FSDF_DEPTH_F64 = 0, FSDF_DEPTH_F32 = 1, FSDF_DEPTH_U16 = 2 };
 int fsdf_set_depth_device(fsdf_ctx* ctx, const void* d_depth, int32_t format, const double* pose, const double* range);
 int fsdf_get_depth_pixels(fsdf_ctx* ctx, int32_t* pixels_out /* [n], caller order, or NULL */, int64_t* n_out);
+
+/* ---- free space ------------------------------------------------------------------
+ * A resident point is a surface observation: Σ ρ(d*) pulls the nearest model
+ * surface onto it. A depth pixel also says that the ray up to its return is
+ * empty, and nothing above sees that: a body in front of what the camera saw,
+ * nearest to no observed point, has zero gradient. A FREE-SPACE SAMPLE is a
+ * position known to be empty, penalised only where the model covers it.
+ *
+ * The objective. The resident cloud may be split in the CALLER'S order: points
+ * [0, n_surface) are surface observations as above, points [n_surface, n) are
+ * free-space samples. With the gate g = (d* < 0) a sample's terms are
+ * ρ -> g ? ρ(d*) : 0 and w -> g ? w(d*) : 0 under the context's loss, times the
+ * point's weight a when weights are set; from there the sums are those of the
+ * two sections above (a ρ, aw, 2 (aw d*) v, Σ aw v vᵀ, Σ aw). Under
+ * FSDF_LOSS_SQUARE the samples' cost is Σ min(d*, 0)², which is C¹; its
+ * Gauss-Newton moments are those of the active set. A gated-out sample stays in
+ * the sums as zero terms, exactly as a weight-0 point does: the summation order
+ * remains a function of the cloud layout alone, and the results are the bits of
+ * the weighted reduction given weights a · g. The reduction (csrc/robust.hip,
+ * its ONE_SIDED instantiations; the gate: csrc/robust_impl.h) reads the
+ * cloud's resident-to-caller permutation: resident point i is a sample iff
+ * permutation[i] >= n_surface (no permutation: i). Nothing is gathered and
+ * nothing goes stale across fsdf_regroup_points. The pass kernels are not
+ * involved.
+ *
+ * fsdf_set_free_split: 0 <= n_surface <= n of the resident cloud (beyond:
+ * FSDF_ERR_ARG, the earlier split stays). n_surface == n or a negative value
+ * clears it. The split belongs to the resident cloud like the weights: every
+ * call that makes another cloud resident clears it (fsdf_set_points, _device,
+ * _prefetched, _range*, _keyed_device, and a depth frame, which sets its own,
+ * below). On a ranged or keyed cloud it is FSDF_ERR_STATE. fsdf_get_free_split:
+ * *n_surface_out (n when none is set) and *set_out; either may be NULL.
+ *
+ * With a split set, on a hull-only rigid scene: fsdf_eval_robust,
+ * fsdf_value_and_gradient and fsdf_value_gradient_hessian evaluate the split
+ * objective through the robust path, also under FSDF_LOSS_SQUARE and without
+ * weights; fsdf_descend and fsdf_descend_lm inherit it through their host
+ * loops. The refusals are the loss's and name the split: a scene with an RBF
+ * skin or a deformation is FSDF_ERR_STATE; the device loops do not serve it
+ * (fsdf_set_solver 1 / 3 and fsdf_set_lm_solver 1 take the host loop, the
+ * required modes return FSDF_ERR_STATE). The least-squares calls listed above
+ * ignore it. With no split every call returns the bits it returned before.
+ *
+ * Samples from a depth frame. fsdf_set_free_space: a context setting like the
+ * sensor and the loss, kept over frames. samples = J in 0..16 per sending pixel
+ * (0: off; stride and lengths are then ignored), stride >= 1, lengths = {gap,
+ * spacing, miss_range}, each finite and >= 0, spacing > 0 when J > 1; anything
+ * else is FSDF_ERR_ARG and the earlier setting stays. fsdf_get_free_space reads
+ * it back (any output may be NULL). With J > 0 every fsdf_set_depth_* makes
+ * resident the observed points FOLLOWED BY the samples, and sets the split
+ * itself to n_surface = the number of valid pixels. Per pixel i = row·cols +
+ * col with row % stride == 0 and col % stride == 0, in this operation order and
+ * uncontracted (s and valid as in "depth frames"):
+ *   L = s − gap                for a valid pixel;
+ *   L = miss_range             for a miss when miss_range > 0 — a pixel that is
+ *                              not valid and not too near, !(s > 0 && s < near):
+ *                              NaN, <= 0, beyond far, +inf;
+ *   otherwise the pixel sends nothing.
+ *   The pixel sends all J samples iff L − (double)(J − 1)·spacing > 0, else none.
+ *   Sample j = 1..J: t = L − (double)(j − 1)·spacing along the pixel's direction u,
+ *   c = (t·u_x, t·u_y, t·u_z), p_k = ((R_k0·c_x + R_k1·c_y) + R_k2·c_z) + t_k.
+ * For FSDF_DEPTH_Z sensors t, gap, spacing and miss_range are in z units; the
+ * point is on the ray either way. The caller order of the samples is j-major,
+ * then pixel row-major: with m sending pixels, sample j of the r-th sending
+ * pixel is caller point n_surface + (j − 1)·m + r. fsdf_get_depth_pixels
+ * returns the pixel of every one of the n points, samples included, so
+ * per-pixel confidences work through fsdf_set_point_weights with one weight per
+ * resident point. flash/depthsensors.py free_space_points restates the
+ * arithmetic: the same bits. The ingest is the depth frame's (csrc/depth.hip):
+ * the count, the scan and the scatter with a second predicate and a second
+ * total, both totals read back in the frame's one sizing synchronisation, and
+ * the combined cloud goes through the path of fsdf_set_points_device as before.
+ * More than 2^31 − 1 points in all is FSDF_ERR_ARG before anything resident is
+ * replaced. With J = 0 a depth frame runs the launches it ran before.
+ *
+ * The solver loops' n_points divisor is the caller's as before: for a frame it
+ * is the resident point count, samples included.
+ *
+ * Not done: the device solver loops with a split; RBF or deformable scenes;
+ * ranged, keyed or sharded free-space frames; a prefetched depth frame; samples
+ * whose count varies per pixel; a visibility (model-to-image) term, which would
+ * need the raycaster inside the loop. */
+int fsdf_set_free_split(fsdf_ctx* ctx, int64_t n_surface);
+int fsdf_get_free_split(const fsdf_ctx* ctx, int64_t* n_surface_out, int32_t* set_out);
+int fsdf_set_free_space(fsdf_ctx* ctx, int32_t samples /* J, 0..16; 0 = off */, int32_t stride /* >= 1 */,
+                        const double* lengths /* [3]: gap >= 0, spacing > 0, miss_range >= 0 */);
+int fsdf_get_free_space(const fsdf_ctx* ctx, int32_t* samples_out, int32_t* stride_out, double* lengths_out /* [3] */);
 
 /* ---- Gauss-Newton for RBF skins: device side -----------------------------------
  * The skins' second moments M_r above, reduced on the device

@@ -189,6 +189,45 @@ function depth_pixels(ctx::Context, cols::Integer)
     [(div(p, cols) + 1, rem(p, cols) + 1) for p in pix]
 end
 
+"""
+The free-space samples every later set_depth! sends after its observed points (fsdf_set_free_space):
+`samples` = J in 1..16 per sending pixel on every `stride`-th row and column, at ranges
+s - gap - (j - 1) * spacing along the pixel's ray (a miss, when miss_range > 0: from miss_range), only
+where the last one stays in front of the camera. The frame then sets the split of the resident
+cloud itself: the samples count only where the model covers them (d* < 0). `samples = 0` turns it off.
+"""
+function set_free_space!(ctx::Context, samples::Integer, stride::Integer=1; gap::Float64=0.02,
+                         spacing::Float64=0.05, miss_range::Float64=0.0)
+    lengths = Float64[gap, spacing, miss_range]
+    check(ctx.ptr, ccall((:fsdf_set_free_space, lib), Cint, (Ptr{Void}, Int32, Int32, Ptr{Float64}),
+                         ctx.ptr, Int32(samples), Int32(stride), lengths), "set_free_space")
+end
+
+"(samples, stride, gap, spacing, miss_range) as the library holds them; samples 0: off (fsdf_get_free_space)."
+function free_space(ctx::Context)
+    samples, stride, lengths = Ref{Int32}(0), Ref{Int32}(0), zeros(Float64, 3)
+    check(ctx.ptr, ccall((:fsdf_get_free_space, lib), Cint, (Ptr{Void}, Ref{Int32}, Ref{Int32}, Ptr{Float64}),
+                         ctx.ptr, samples, stride, lengths), "get_free_space")
+    (Int(samples[]), Int(stride[]), lengths[1], lengths[2], lengths[3])
+end
+
+"""
+Points n_surface + 1 : n of the resident cloud, in the order given to set_points!, are free-space
+samples: positions known to be empty, which count only where the model covers them (fsdf_set_free_split;
+the robust path, also without a loss). `n_surface` = n or a negative value clears it; every new cloud does.
+"""
+set_free_split!(ctx::Context, n_surface::Integer) =
+    check(ctx.ptr, ccall((:fsdf_set_free_split, lib), Cint, (Ptr{Void}, Int64), ctx.ptr, Int64(n_surface)),
+          "set_free_split")
+
+"n_surface of the resident cloud, or `nothing` when no split is set (fsdf_get_free_split)."
+function free_split(ctx::Context)
+    n, set = Ref{Int64}(0), Ref{Int32}(0)
+    check(ctx.ptr, ccall((:fsdf_get_free_split, lib), Cint, (Ptr{Void}, Ref{Int64}, Ref{Int32}), ctx.ptr, n, set),
+          "get_free_split")
+    set[] == 0 ? nothing : Int(n[])
+end
+
 "One GPU's shard of the frame's cloud (the cost is a sum over points,
 src/gradientdescent.jl:32): the whole cloud is Hilbert-sorted on the device and
 this context keeps the contiguous range [first, last] (1-based, inclusive) of

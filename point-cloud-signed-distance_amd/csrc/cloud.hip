@@ -90,6 +90,7 @@ static int set_points_impl(fsdf_ctx* c, const double* src, int64_t n, bool devic
   if (rc0) return rc0;
   c->n = 0;
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
+  c->free_split = -1;                    // (and so does the split of its free-space samples)
   c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
   const double* d_src = src;
   if (!device_src && n > 0) {
@@ -180,6 +181,7 @@ static int finish_resident(fsdf_ctx* c, int64_t n, bool ranged, bool spheres_don
   }
   c->seed_pending = false;
   c->conf_set = c->conf_stale = false;  // (a new cloud: no weights until fsdf_set_point_weights)
+  c->free_split = -1;                    // (and no free-space samples until fsdf_set_free_split)
   c->regrouped = false;
   c->regroup_pending = true;  // (the auto regroup follows the new cloud's first iteration pass)
   c->last_pass_shape = 0;
@@ -246,6 +248,7 @@ extern "C" int fsdf_set_points_keyed_device(fsdf_ctx* c, const double* d_xyz, co
   HIPCHECK(c, hipStreamSynchronize(c->stream));
   c->n = 0;
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
+  c->free_split = -1;                    // (and so does the split of its free-space samples)
   c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
   HIPCHECK(c, c->cur.pts.reserve((size_t)std::max<int64_t>(n, 1) * 3 * point_bytes(c)));
   HIPCHECK(c, c->cur.perm.reserve((size_t)std::max<int64_t>(n, 1)));
@@ -355,12 +358,16 @@ static int set_depth_impl(fsdf_ctx* c, const void* depth, int format, bool devic
   }
   const int64_t npix = (int64_t)c->sensor_rows * c->sensor_cols;
   const size_t nblocks = (size_t)((npix + 255) / 256);
+  // free-space samples (fsdf_set_free_space): a second predicate and a second total in the same launches
+  const int J = c->free_samples;
+  const fsdf::DepthFree F = {J, c->free_stride, c->sensor_cols, c->free_gap, c->free_spacing, c->free_miss};
+  const fsdf::DepthFree* Fp = J > 0 ? &F : nullptr;
   HIPCHECK(c, hipSetDevice(c->device));
   // the previous frame's work may still read the staging buffer and the buffers a reserve frees
   HIPCHECK(c, hipStreamSynchronize(c->stream));
-  HIPCHECK(c, c->depth_counts.reserve(nblocks));
-  HIPCHECK(c, c->depth_total.reserve(1));
-  HIPCHECK(c, c->h_depth_total.reserve(1));
+  HIPCHECK(c, c->depth_counts.reserve(2 * nblocks));
+  HIPCHECK(c, c->depth_total.reserve(2));
+  HIPCHECK(c, c->h_depth_total.reserve(2));
   const void* d_depth = depth;
   if (!device_src) {
     const size_t bytes = (size_t)npix * fsdf::depth_format_bytes(format);
@@ -368,25 +375,97 @@ static int set_depth_impl(fsdf_ctx* c, const void* depth, int format, bool devic
     HIPCHECK(c, hipMemcpyAsync(c->depth_raw.get(), depth, bytes, hipMemcpyHostToDevice, c->stream));
     d_depth = c->depth_raw.get();
   }
-  hipError_t e = fsdf::launch_depth_count(format, d_depth, npix, r, c->depth_counts.get(), c->depth_total.get(), c->stream);
+  hipError_t e = fsdf::launch_depth_count(format, d_depth, npix, r, Fp, c->depth_counts.get(), c->depth_total.get(),
+                                          c->stream);
   if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "%s (count): %s", who, hipGetErrorString(e));
-  HIPCHECK(c, hipMemcpyAsync(c->h_depth_total.get(), c->depth_total.get(), sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  // (both totals in the one read-back that sizes the cloud)
+  HIPCHECK(c, hipMemcpyAsync(c->h_depth_total.get(), c->depth_total.get(), (Fp ? 2 : 1) * sizeof(int64_t),
+                             hipMemcpyDeviceToHost, c->stream));
   HIPCHECK(c, hipStreamSynchronize(c->stream));
-  const int64_t n = *c->h_depth_total.get();
-  if (n < 0 || n > npix) return fail(c, FSDF_ERR_HIP, "%s: %lld valid pixels of %lld", who, (long long)n, (long long)npix);
+  const int64_t n_surface = c->h_depth_total.get()[0], m = Fp ? c->h_depth_total.get()[1] : 0;
+  if (n_surface < 0 || n_surface > npix)
+    return fail(c, FSDF_ERR_HIP, "%s: %lld valid pixels of %lld", who, (long long)n_surface, (long long)npix);
+  if (m < 0 || m > npix)
+    return fail(c, FSDF_ERR_HIP, "%s: %lld pixels of %lld send free-space samples", who, (long long)m, (long long)npix);
+  const int64_t n = n_surface + (int64_t)J * m;
+  if (n > INT32_MAX)
+    return fail(c, FSDF_ERR_ARG,
+                "%s: %lld points and %d x %lld free-space samples (fsdf_set_free_space) exceed 2^31 - 1 points; the "
+                "resident cloud stays", who, (long long)n_surface, J, (long long)m);
   // (the resident cloud's pixel list is overwritten from here on: whatever
   // happens next, it no longer names a depth frame's pixels)
   c->depth_cloud = false;
   HIPCHECK(c, c->staging.reserve((size_t)std::max<int64_t>(n, 1) * 3));
   HIPCHECK(c, c->depth_pix.reserve((size_t)std::max<int64_t>(n, 1)));
   if (n > 0) {
-    e = fsdf::launch_depth_scatter(format, d_depth, c->sensor_u.get(), npix, r, P, c->depth_counts.get(), c->staging.get(),
-                                   c->depth_pix.get(), c->stream);
+    e = fsdf::launch_depth_scatter(format, d_depth, c->sensor_u.get(), npix, r, P, Fp, n_surface, m,
+                                   c->depth_counts.get(), c->staging.get(), c->depth_pix.get(), c->stream);
     if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "%s (scatter): %s", who, hipGetErrorString(e));
   }
   const int rc = set_points_impl(c, c->staging.get(), n, true, 0, n);
   if (rc) return rc;
   c->depth_cloud = true;
+  c->free_split = n_surface < n ? n_surface : -1;  // (the samples follow the observed points; none: no split)
+  return FSDF_OK;
+}
+
+// ---- free space (include/flashsdf.h "free space") --------------------------------
+extern "C" int fsdf_set_free_split(fsdf_ctx* c, int64_t n_surface) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n_surface < 0 || n_surface == c->n) {  // clear: every point is a surface observation again
+    c->free_split = -1;
+    return FSDF_OK;
+  }
+  if (c->ranged)
+    return fail(c, FSDF_ERR_STATE, "set_free_split: a split serves a whole resident cloud (not a ranged or keyed one)");
+  if (n_surface > c->n)
+    return fail(c, FSDF_ERR_ARG, "set_free_split: n_surface %lld of a resident cloud of %lld points; the earlier split stays",
+                (long long)n_surface, (long long)c->n);
+  c->free_split = n_surface;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_get_free_split(const fsdf_ctx* c, int64_t* n_surface_out, int32_t* set_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (n_surface_out) *n_surface_out = c->free_split >= 0 ? c->free_split : c->n;
+  if (set_out) *set_out = c->free_split >= 0 ? 1 : 0;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_set_free_space(fsdf_ctx* c, int32_t samples, int32_t stride, const double* lengths) {
+  if (!c) return FSDF_ERR_ARG;
+  if (samples == 0) {  // off (stride and lengths ignored)
+    c->free_samples = 0;
+    return FSDF_OK;
+  }
+  if (samples < 0 || samples > 16)
+    return fail(c, FSDF_ERR_ARG, "set_free_space: %d samples per pixel (0 to 16); the earlier setting stays", samples);
+  if (stride < 1) return fail(c, FSDF_ERR_ARG, "set_free_space: stride %d (>= 1); the earlier setting stays", stride);
+  if (!lengths) return fail(c, FSDF_ERR_ARG, "set_free_space: null lengths; the earlier setting stays");
+  const double gap = lengths[0], spacing = lengths[1], miss = lengths[2];
+  const double big = 1.79769313486231570815e308;
+  if (!(gap >= 0.0 && gap <= big) || !(spacing >= 0.0 && spacing <= big) || !(miss >= 0.0 && miss <= big) ||
+      (samples > 1 && !(spacing > 0.0)))  // (a NaN fails the first test of each)
+    return fail(c, FSDF_ERR_ARG,
+                "set_free_space: gap %g, spacing %g, miss_range %g (finite and >= 0, spacing > 0 with more than one "
+                "sample); the earlier setting stays", gap, spacing, miss);
+  c->free_samples = samples;
+  c->free_stride = stride;
+  c->free_gap = gap;
+  c->free_spacing = spacing;
+  c->free_miss = miss;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_get_free_space(const fsdf_ctx* c, int32_t* samples_out, int32_t* stride_out, double* lengths_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (samples_out) *samples_out = c->free_samples;
+  if (stride_out) *stride_out = c->free_stride;
+  if (lengths_out) {
+    lengths_out[0] = c->free_gap;
+    lengths_out[1] = c->free_spacing;
+    lengths_out[2] = c->free_miss;
+  }
   return FSDF_OK;
 }
 
@@ -494,6 +573,7 @@ extern "C" int fsdf_set_points_prefetched(fsdf_ctx* c) {
   if (rc) return rc;
   c->n = 0;
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
+  c->free_split = -1;                    // (and so does the split of its free-space samples)
   c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
   std::swap(c->cur, c->next);
   return finish_resident(c, n, false, true);

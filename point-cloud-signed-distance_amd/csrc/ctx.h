@@ -200,6 +200,14 @@ struct fsdf_ctx {
   fsdf::DevBuf<int64_t> depth_total;
   fsdf::PinnedBuf<int64_t> h_depth_total;
   bool depth_cloud = false;
+  // free space (fsdf_set_free_split, fsdf_set_free_space; robust.hip ONE_SIDED, depth.hip): free_split
+  // is the resident cloud's n_surface — caller points [free_split, n) are free-space samples — and
+  // belongs to the cloud like the weights (-1: none; every new cloud clears it). The samples a depth
+  // frame sends are a context setting like the sensor (free_samples 0: off); a frame with them on
+  // reads two totals back (depth_total / h_depth_total [2], depth_counts [2][blocks]).
+  int64_t free_split = -1;
+  int free_samples = 0, free_stride = 1;
+  double free_gap = 0.0, free_spacing = 0.0, free_miss = 0.0;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;
@@ -294,7 +302,9 @@ void robust_rows_finish(fsdf_ctx* c, bool moments);
 // point_weights.hip: the weights in resident order for a robust launch (null: none set), regathered
 // on the context stream when the layout changed since; whether the iteration calls take the robust path
 int point_weights_resident(fsdf_ctx* c, const double** d_conf_out);
-static inline bool robust_objective(const fsdf_ctx* c) { return c->loss_kind != FSDF_LOSS_SQUARE || c->conf_set; }
+static inline bool robust_objective(const fsdf_ctx* c) {
+  return c->loss_kind != FSDF_LOSS_SQUARE || c->conf_set || c->free_split >= 0;
+}
 int fetch(fsdf_ctx* c, int64_t n, double* cost_out, double* accum_out, int32_t* kstar_out, double* d_out,
           double* grad_out, bool want_pp);
 // iterate.hip (the solver loops of descend.hip run on them)

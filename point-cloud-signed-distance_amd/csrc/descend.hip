@@ -164,7 +164,9 @@ static int descend_checks(fsdf_ctx* c, const char* who, const double* x, int32_t
   if (!x || iteration_limit < 0 || !(n_points > 0.0) || !std::isfinite(gain) || !(max_step >= 0.0))
     return fail(c, FSDF_ERR_ARG, "%s: bad arguments", who);
   if (c->mech.nb == 0) return fail(c, FSDF_ERR_STATE, "%s: no mechanism (call fsdf_set_mechanism)", who);
-  if (rigid_only) return fail(c, FSDF_ERR_STATE, "%s: rigid scenes only (no RBF skin, no deformation)", who);
+  if (rigid_only)
+    return fail(c, FSDF_ERR_STATE, "%s: rigid scenes only (no RBF skin, no deformation)%s", who,
+                c->free_split >= 0 ? "; a free-space split is set (fsdf_set_free_split)" : "");
   if ((int)c->mech.surface_body.size() != c->lm.S || (int)c->mech.poses.size() != 12 * c->lm.S)
     return fail(c, FSDF_ERR_STATE, "%s: mechanism registered for another surface list (call fsdf_set_mechanism)", who);
   return FSDF_OK;
@@ -297,12 +299,13 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
   }
   // A loss other than SQUARE (fsdf_set_loss) is served by the host loop alone
   // (the device step reads the pass's least-squares accumulator).
-  // Per-point weights (fsdf_set_point_weights) likewise.
+  // Per-point weights (fsdf_set_point_weights) and a free-space split (fsdf_set_free_split) likewise.
   const bool loss = robust_objective(c);
   if (loss && required && iteration_limit > 0)
     return fail(c, FSDF_ERR_STATE,
                 "descend: the device loop was required (fsdf_set_solver %d) but %s (the host loop serves it)",
                 c->solver_device,
+                c->free_split >= 0 ? "a free-space split is set (fsdf_set_free_split)" :
                 c->conf_set ? "per-point weights are set (fsdf_set_point_weights)" :
                 c->loss_kind == FSDF_LOSS_HUBER ? "a loss is set (fsdf_set_loss kind 1)" :
                                                   "a loss is set (fsdf_set_loss kind 2)");
@@ -556,11 +559,12 @@ extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, 
   // step's raises of a degenerate factorisation are then bounded), resident
   // points, the moments table and both solver kernels' carves within their LDS
   // A loss other than SQUARE (fsdf_set_loss): the host loop alone (mode 1 takes it, mode 2 is refused).
-  // Per-point weights (fsdf_set_point_weights) likewise.
+  // Per-point weights (fsdf_set_point_weights) and a free-space split (fsdf_set_free_split) likewise.
   const bool loss = robust_objective(c);
   if (loss && c->lm_solver_device == 2)
     return fail(c, FSDF_ERR_STATE, "descend_lm: the device loop was required (fsdf_set_lm_solver 2) but %s "
                                    "(loss kind %d: the host loop serves it)",
+                c->free_split >= 0 ? "a free-space split is set (fsdf_set_free_split)" :
                 c->conf_set ? "per-point weights are set (fsdf_set_point_weights)" : "a loss is set (fsdf_set_loss)",
                 c->loss_kind);
   if (rigid && c->lm_solver_device && iteration_limit > 0 && !loss) {

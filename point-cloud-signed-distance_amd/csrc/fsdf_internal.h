@@ -295,9 +295,14 @@ size_t robust_partials_len(int64_t n, int S);
 // (moments) or [S][8]. A k* outside [0, S) contributes nothing. d_conf: null, or
 // [n] per-point confidence weights in resident order (fp64 in either precision):
 // the WEIGHTED instantiations, aw = a · w in place of w and a · ρ in place of ρ.
+// n_surface >= 0: the ONE_SIDED instantiations — resident point i is a
+// free-space sample iff (d_perm ? d_perm[i] : i) >= n_surface (d_perm: null, or
+// the cloud's resident→caller permutation [n]) and then counts only where
+// d* < 0 (robust_impl.h one_sided_factor); n_surface < 0: no split, d_perm unread.
 hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
-                         const double* d_grad, const double* d_conf, int64_t n, int S, int kind, double scale,
-                         double* d_partials, double* d_rows, hipStream_t s);
+                         const double* d_grad, const double* d_conf, const int32_t* d_perm, int64_t n_surface,
+                         int64_t n, int S, int kind, double scale, double* d_partials, double* d_rows,
+                         hipStream_t s);
 // res[i] = src[perm[i]] over n doubles (point_weights.hip: a per-point side array
 // into resident order; an index outside [0, n) reads as 0)
 hipError_t launch_gather_f64(const double* d_src, const int32_t* d_perm, int64_t n, double* d_res, hipStream_t s);
@@ -316,12 +321,25 @@ struct DepthRange {
 struct DepthPose {
   double R[9], t[3];
 };
+// Free-space samples (fsdf_set_free_space; `free` null: none, the launches and
+// buffers above): a pixel on the stride grid with free length L (s − gap of a
+// valid pixel; miss_range of a miss when that is > 0) and
+// L − (samples − 1) · spacing > 0 sends `samples` points at ranges
+// t = L − (j − 1) · spacing along its direction, after the valid pixels' points:
+// sample j of the r-th sending pixel at n_surface + (j − 1) · m + r. The count
+// then fills d_counts [2][blocks] (valid, sending), the scan runs one workgroup
+// per row and writes d_total [2]; the scatter, given both totals, writes
+// d_xyz / d_pix [n_surface + samples · m].
+struct DepthFree {
+  int32_t samples, stride, cols;
+  double gap, spacing, miss_range;
+};
 size_t depth_format_bytes(int format);
-hipError_t launch_depth_count(int format, const void* d_depth, int64_t npix, const DepthRange& r, int32_t* d_counts,
-                              int64_t* d_total, hipStream_t s);
+hipError_t launch_depth_count(int format, const void* d_depth, int64_t npix, const DepthRange& r,
+                              const DepthFree* free, int32_t* d_counts, int64_t* d_total, hipStream_t s);
 hipError_t launch_depth_scatter(int format, const void* d_depth, const double* d_u, int64_t npix, const DepthRange& r,
-                                const DepthPose& P, const int32_t* d_offsets, double* d_xyz, int32_t* d_pix,
-                                hipStream_t s);
+                                const DepthPose& P, const DepthFree* free, int64_t n_surface, int64_t m,
+                                const int32_t* d_offsets, double* d_xyz, int32_t* d_pix, hipStream_t s);
 
 // ---- second moments of RBF skins (skin_moments.hip) ----------------------------
 // Per skin r of n centres, m = 4n + 4: M_r [m][m] = Σ_{p: k*(p) = r's surface}

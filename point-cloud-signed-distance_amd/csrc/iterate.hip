@@ -255,8 +255,9 @@ double g_host_t[8];  // (ctx.h: the host loop's clocks, printed by fsdf_descend)
 long g_host_n;
 #endif
 
-// With a loss other than SQUARE set (fsdf_set_loss), or per-point weights
-// (fsdf_set_point_weights: then also under SQUARE): the same iteration on the
+// With a loss other than SQUARE set (fsdf_set_loss), per-point weights
+// (fsdf_set_point_weights) or a free-space split (fsdf_set_free_split; both
+// also under SQUARE): the same iteration on the
 // robust objective Σρ(d*) — the pass with k*, d*, ∇d* in resident order, the
 // robust launch (robust.hip) in place of the pass's own sums, and the same
 // chain rule on the accumulator assembled from its rows. The auto regroup is
@@ -266,8 +267,9 @@ static int robust_iteration(fsdf_ctx* c, const double* x, double* cost_out, doub
                             const char* who) {
   if (c->lm.R > 0 || c->mech.n_deform > 0)
     return fail(c, FSDF_ERR_STATE,
-                "%s: the loss set by fsdf_set_loss (kind %d)%s serves rigid scenes (no RBF skin, no deformation)", who,
-                c->loss_kind, c->conf_set ? " and the weights of fsdf_set_point_weights" : "");
+                "%s: the loss set by fsdf_set_loss (kind %d)%s%s serves rigid scenes (no RBF skin, no deformation)", who,
+                c->loss_kind, c->conf_set ? " and the weights of fsdf_set_point_weights" : "",
+                c->free_split >= 0 ? " and the free-space split of fsdf_set_free_split" : "");
   int rc = iteration_prepare(c, x, who);
   if (rc) return rc;
   auto& M = c->mech;

@@ -515,7 +515,8 @@ extern "C" int fsdf_get_loss(const fsdf_ctx* c, int32_t* kind_out, double* scale
 int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool moments) {
   const int S = c->lm.S;
   if (c->lm.R > 0 || c->mech.n_deform > 0)
-    return fail(c, FSDF_ERR_STATE, "%s: a robust loss serves hull-only scenes (no RBF skin, no deformation)", who);
+    return fail(c, FSDF_ERR_STATE, "%s: a robust loss%s serves hull-only scenes (no RBF skin, no deformation)", who,
+                c->free_split >= 0 ? " or a free-space split (fsdf_set_free_split)" : "");
   if (!fsdf::robust_fit(S))
     return fail(c, FSDF_ERR_STATE,
                 "%s: the robust table of %d surfaces (%zu bytes) does not fit %d bytes of LDS (at most 282 surfaces)",
@@ -549,8 +550,10 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
     memset(h_rows, 0, rlen * sizeof(double));
     return FSDF_OK;
   }
-  HIPCHECK(c, fsdf::launch_robust(c->precision, moments, d_pts, d_kstar, d_d, d_grad, d_conf, n, S, c->loss_kind,
-                                  c->loss_scale, d_partials, d_rows, c->stream));
+  // (a split: the one-sided instantiations, which read the resident→caller permutation — null: the
+  // resident order is the caller's)
+  HIPCHECK(c, fsdf::launch_robust(c->precision, moments, d_pts, d_kstar, d_d, d_grad, d_conf, c->cur.perm.get(),
+                                  c->free_split, n, S, c->loss_kind, c->loss_scale, d_partials, d_rows, c->stream));
   HIPCHECK(c, hipMemcpyAsync(h_rows, d_rows, rlen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   return FSDF_OK;
 }
@@ -582,7 +585,9 @@ extern "C" int fsdf_eval_robust(fsdf_ctx* c, const double* poses, double* cost_o
   if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval_robust: no model (call fsdf_set_model first)");
   if (!poses) return fail(c, FSDF_ERR_ARG, "eval_robust: poses required");
   HIPCHECK(c, hipSetDevice(c->device));
-  if (c->lm.R > 0) return fail(c, FSDF_ERR_STATE, "eval_robust: hull-only scenes (the scene has an RBF skin)");
+  if (c->lm.R > 0)
+    return fail(c, FSDF_ERR_STATE, "eval_robust: hull-only scenes (the scene has an RBF skin)%s",
+                c->free_split >= 0 ? "; a free-space split is set (fsdf_set_free_split)" : "");
   const bool moments = moments_out != nullptr;
   const int rc = run_pass_robust(c, poses, "eval_robust", moments);
   if (rc) return rc;

@@ -28,6 +28,15 @@
 // aw = a · w stands wherever w does (the moments, wrench_scale(aw, d), Σw), and
 // a · ρ in the cost. A point of weight 0 stays in the sums as zero terms: the
 // summation order is the unweighted kernel's, a function of the layout alone.
+//
+// ONE_SIDED (fsdf_set_free_split): caller points [n_surface, n) are free-space
+// samples, penalised only where the model covers them (d* < 0). Resident point
+// i is one iff (perm ? perm[i] : i) >= n_surface — the cloud's resident→caller
+// permutation, read here (4 B per point): nothing is gathered, nothing goes
+// stale across a regroup. The gate (robust_impl.h one_sided_factor) replaces a
+// by 0.0 for a sample outside the model and the WEIGHTED arithmetic follows, so
+// the bits are those of the weighted kernel given weights a · gate; table, run
+// and wave layout are unchanged.
 
 #include <hip/hip_runtime.h>
 
@@ -70,15 +79,17 @@ size_t robust_partials_len(int64_t n, int S) {
 extern __shared__ __attribute__((aligned(16))) double robust_tab[];  // [waves][S][LEN]
 
 // blockDim.x / 64 waves; run is a multiple of them
-template <typename T, bool MOMENTS, bool WEIGHTED>
+template <typename T, bool MOMENTS, bool WEIGHTED, bool ONE_SIDED>
 __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restrict__ pts,
                                                               const int32_t* __restrict__ kstar,
                                                               const double* __restrict__ dstar,
                                                               const double* __restrict__ grad, int64_t n, int S,
                                                               int run, int kind, double scale,
                                                               double* __restrict__ partials,
-                                                              const double* __restrict__ conf) {
+                                                              const double* __restrict__ conf,
+                                                              const int32_t* __restrict__ perm, int64_t n_surface) {
   constexpr int LEN = MOMENTS ? kRobustLen : kRobustTail;
+  constexpr bool FACTOR = WEIGHTED || ONE_SIDED;  // a point's terms carry a factor a
   constexpr int M0 = LEN - kRobustTail;  // the wrench's first entry; Σρ at M0 + 6, Σw at M0 + 7
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
   const int len = LEN * S;
@@ -133,8 +144,9 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
       v[3] = py * v[2] - pz * v[1];
       v[4] = pz * v[0] - px * v[2];
       v[5] = px * v[1] - py * v[0];
-      const double a = WEIGHTED ? conf[i] : 1.0;
-      const double w = WEIGHTED ? a * robust::weight(kind, scale, d) : robust::weight(kind, scale, d);  // aw
+      double a = WEIGHTED ? conf[i] : 1.0;
+      if (ONE_SIDED) a = robust::one_sided_factor(robust::free_sample(perm ? (int64_t)perm[i] : i, n_surface), d, a);
+      const double w = FACTOR ? a * robust::weight(kind, scale, d) : robust::weight(kind, scale, d);  // aw
       if (MOMENTS) {
         int e = 0;
 #pragma unroll
@@ -147,7 +159,7 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
       const double t = robust::wrench_scale(w, d);
 #pragma unroll
       for (int a = 0; a < 6; ++a) acc[M0 + a] += t * v[a];
-      acc[M0 + 6] += WEIGHTED ? a * robust::rho(kind, scale, d) : robust::rho(kind, scale, d);
+      acc[M0 + 6] += FACTOR ? a * robust::rho(kind, scale, d) : robust::rho(kind, scale, d);
       acc[M0 + 7] += w;
       ck = k;
     }
@@ -164,30 +176,38 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
 }
 
 hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
-                         const double* d_grad, const double* d_conf, int64_t n, int S, int kind, double scale,
-                         double* d_partials, double* d_rows, hipStream_t s) {
+                         const double* d_grad, const double* d_conf, const int32_t* d_perm, int64_t n_surface,
+                         int64_t n, int S, int kind, double scale, double* d_partials, double* d_rows,
+                         hipStream_t s) {
   if (n <= 0 || !robust_fit(S) || !robust::valid(kind, scale) || !d_pts || !d_kstar || !d_d || !d_grad ||
       !d_partials || !d_rows)
     return hipErrorInvalidValue;
   const int groups = robust_groups(n), run = (int)robust_run(n), waves = robust_waves(S), block = 64 * waves;
   const int len = moments ? kRobustLen : kRobustTail;
   const size_t lds = (size_t)waves * S * len * sizeof(double);
-#define FSDF_ROBUST_LAUNCH(T, M, W)                                                                              \
-  hipLaunchKernelGGL((robust_kernel<T, M, W>), dim3(groups), dim3(block), lds, s, (const T*)d_pts, d_kstar, d_d, \
-                     d_grad, n, S, run, kind, scale, d_partials, d_conf)
-#define FSDF_ROBUST_LAUNCH_M(T, W)              \
-  do {                                          \
-    if (moments) FSDF_ROBUST_LAUNCH(T, true, W); \
-    else FSDF_ROBUST_LAUNCH(T, false, W);        \
+#define FSDF_ROBUST_LAUNCH(T, M, W, O)                                                                         \
+  hipLaunchKernelGGL((robust_kernel<T, M, W, O>), dim3(groups), dim3(block), lds, s, (const T*)d_pts, d_kstar, \
+                     d_d, d_grad, n, S, run, kind, scale, d_partials, d_conf, d_perm, n_surface)
+#define FSDF_ROBUST_LAUNCH_M(T, W, O)              \
+  do {                                             \
+    if (moments) FSDF_ROBUST_LAUNCH(T, true, W, O); \
+    else FSDF_ROBUST_LAUNCH(T, false, W, O);        \
   } while (0)
-  // (d_conf null: the unweighted instantiations, which never read it)
+#define FSDF_ROBUST_LAUNCH_W(T, O)                 \
+  do {                                             \
+    if (d_conf) FSDF_ROBUST_LAUNCH_M(T, true, O);  \
+    else FSDF_ROBUST_LAUNCH_M(T, false, O);        \
+  } while (0)
+  // (d_conf null: the unweighted instantiations, which never read it; n_surface < 0: no split — the
+  // instantiations that read neither the permutation nor d* for a gate)
   if (precision == 64) {
-    if (d_conf) FSDF_ROBUST_LAUNCH_M(double, true);
-    else FSDF_ROBUST_LAUNCH_M(double, false);
+    if (n_surface >= 0) FSDF_ROBUST_LAUNCH_W(double, true);
+    else FSDF_ROBUST_LAUNCH_W(double, false);
   } else {
-    if (d_conf) FSDF_ROBUST_LAUNCH_M(float, true);
-    else FSDF_ROBUST_LAUNCH_M(float, false);
+    if (n_surface >= 0) FSDF_ROBUST_LAUNCH_W(float, true);
+    else FSDF_ROBUST_LAUNCH_W(float, false);
   }
+#undef FSDF_ROBUST_LAUNCH_W
 #undef FSDF_ROBUST_LAUNCH_M
 #undef FSDF_ROBUST_LAUNCH
   const hipError_t e = hipGetLastError();

@@ -16,6 +16,7 @@
 //               it to 1 − (1 − u²)³'s cancellation); else w = 0 exactly, ρ = c²/3
 #pragma once
 #include <math.h>
+#include <stdint.h>
 
 #include "kin_impl.h"
 
@@ -56,6 +57,17 @@ FSDF_HD double rho(int kind, double c, double d) {
 
 // the factor of v = (∇d*, p × ∇d*) in a point's wrench 2 w d · v
 FSDF_HD double wrench_scale(double w, double d) { return 2.0 * (w * d); }
+
+// Free-space samples (include/flashsdf.h "free space"): caller points
+// [n_surface, n) are positions known to be empty, penalised only where the
+// model covers them. one_sided_factor is the point's factor a in the weighted
+// arithmetic above (a · w, a · ρ): the caller's weight (1.0 without weights)
+// for a surface observation and for a sample with d* < 0, exactly 0.0 for a
+// sample the model does not cover (a NaN d* fails the test) — that point stays
+// in the sums as zero terms, as a weight-0 point does.
+FSDF_HD bool free_sample(int64_t caller_index, int64_t n_surface) { return caller_index >= n_surface; }
+FSDF_HD bool one_sided_gate(double d) { return d < 0.0; }
+FSDF_HD double one_sided_factor(bool free, double d, double a) { return !free || one_sided_gate(d) ? a : 0.0; }
 
 }  // namespace robust
 }  // namespace fsdf

@@ -15,7 +15,7 @@ from .robust import Huber, Tukey
 __all__ = ["BodyGeometry", "ConvexGeometry", "DeformableInterpolatingSkin", "InterpolatingGeometry",
            "Manipulator", "ManipulatorState", "RigidInterpolatingSkin", "SceneSkin", "hull_poses",
            "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError",
-           "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights", "DepthFrame"]
+           "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights", "DepthFrame", "FreeSpace"]
 
 
 def __getattr__(name):
@@ -35,6 +35,9 @@ def __getattr__(name):
     if name == "DepthFrame":  # a depth image, its sensor and pose, taken wherever a sensed cloud is
         from .depthsensors import DepthFrame
         return DepthFrame
+    if name == "FreeSpace":  # a depth frame's free-space samples (DepthFrame(..., free_space=FreeSpace(...)))
+        from .depthsensors import FreeSpace
+        return FreeSpace
     if name == "DepthSensors":
         from . import depthsensors
         return depthsensors

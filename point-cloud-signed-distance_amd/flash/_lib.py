@@ -135,6 +135,10 @@ _PROTOS = {
     "fsdf_set_depth_u16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsdf_set_depth_device": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "fsdf_get_depth_pixels": (c_int32, [c_void_p, c_void_p, POINTER(c_int64)]),
+    "fsdf_set_free_split": (c_int32, [c_void_p, c_int64]),
+    "fsdf_get_free_split": (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int32)]),
+    "fsdf_set_free_space": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
+    "fsdf_get_free_space": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), c_void_p]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -621,6 +625,47 @@ class Context:
         if n.value:
             check(self._lib.fsdf_get_depth_pixels(self._ctx, ptr(out), ctypes.byref(n)), self._ctx, "get_depth_pixels")
         return out
+
+    def set_free_space(self, free_space):
+        """fsdf_set_free_space: the free-space samples every later set_depth
+        sends after its observed points — a depthsensors.FreeSpace (anything
+        with .samples, .stride, .gap, .spacing, .miss_range), or None for none.
+        A context setting like the sensor: frames keep it."""
+        if free_space is None:
+            check(self._lib.fsdf_set_free_space(self._ctx, 0, 1, None), self._ctx, "set_free_space")
+            return
+        f = free_space
+        lengths = np.array([f.gap, f.spacing, f.miss_range], np.float64)
+        check(self._lib.fsdf_set_free_space(self._ctx, int(f.samples), int(f.stride), ptr(lengths)), self._ctx,
+              "set_free_space")
+
+    def get_free_space(self):
+        """fsdf_get_free_space: (samples, stride, gap, spacing, miss_range) as
+        the library holds them, or None when off."""
+        samples, stride, lengths = c_int32(0), c_int32(0), np.zeros(3, np.float64)
+        check(self._lib.fsdf_get_free_space(self._ctx, ctypes.byref(samples), ctypes.byref(stride), ptr(lengths)),
+              self._ctx, "get_free_space")
+        return (samples.value, stride.value, *lengths.tolist()) if samples.value else None
+
+    def set_free_split(self, n_surface):
+        """fsdf_set_free_split: points [n_surface, n) of the resident cloud, in
+        the order of the array it was set from, are free-space samples — they
+        count only where the model covers them (d* < 0) in every sum of
+        eval_robust, value_and_gradient, value_gradient_hessian, descend and
+        descend_lm (hull-only rigid scenes; the robust path, also without a
+        loss). None, n or a negative value clears it. It belongs to the
+        resident cloud: every set_points* clears it, a set_depth with free
+        space on sets its own."""
+        check(self._lib.fsdf_set_free_split(self._ctx, -1 if n_surface is None else int(n_surface)), self._ctx,
+              "set_free_split")
+
+    def get_free_split(self):
+        """fsdf_get_free_split: n_surface of the resident cloud, or None when
+        no split is set."""
+        n, flag = c_int64(0), c_int32(0)
+        check(self._lib.fsdf_get_free_split(self._ctx, ctypes.byref(n), ctypes.byref(flag)), self._ctx,
+              "get_free_split")
+        return n.value if flag.value else None
 
     def eval_skin_moments(self, poses):
         """fsdf_eval_skin_moments: one pass over the resident cloud and the

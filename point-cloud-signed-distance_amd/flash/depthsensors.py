@@ -16,6 +16,13 @@ device back-projects and compacts itself (Context.set_sensor / set_depth,
 csrc/depth.hip) in the order and arithmetic of raycast_points (:99-113);
 depth_points is its numpy twin, bit for bit.
 
+FreeSpace / free_space_points (not in the reference): what a depth image says
+beyond its returns — the ray up to each return is empty, and a pixel with no
+return saw nothing within range. A DepthFrame with `free_space` set sends
+samples along its rays after the observed points (fsdf_set_free_space), which
+the robust reduction penalises only where the model covers them
+(include/flashsdf.h "free space"); free_space_points is the numpy twin.
+
 depth_noise_weights (not in the reference): per-point confidence weights from
 a structured-light sensor's axial noise model, for estimate_state / Tracker /
 track (`weights=`).
@@ -133,6 +140,91 @@ def depth_points(depth, sensor_rays, tform: Transform | None, near: float = 0.0,
     return points, pixels
 
 
+@dataclass(frozen=True)
+class FreeSpace:
+    """The free-space samples of a depth frame (fsdf_set_free_space): `samples`
+    = J points (1..16) per sending pixel, on every `stride`-th row and column.
+    A valid pixel's free length is L = s − gap (gap: the margin kept in front
+    of the return, a few noise sigmas); a miss's — no return: NaN, <= 0, beyond
+    far, +inf, but not a too-near reading — is `miss_range` when that is > 0.
+    A pixel sends its J samples at ranges L − (j − 1) · spacing, j = 1..J, iff
+    the last one is > 0. Lengths are in the units of s = scale · depth (z units
+    for kind "z")."""
+    samples: int = 4
+    stride: int = 1
+    gap: float = 0.02
+    spacing: float = 0.05
+    miss_range: float = 0.0
+
+    def __post_init__(self):
+        if isinstance(self.samples, bool) or int(self.samples) != self.samples or not 1 <= self.samples <= 16:
+            raise ValueError(f"FreeSpace: samples must be an integer in 1..16, got {self.samples!r}")
+        if isinstance(self.stride, bool) or int(self.stride) != self.stride or self.stride < 1:
+            raise ValueError(f"FreeSpace: stride must be an integer >= 1, got {self.stride!r}")
+        for name in ("gap", "spacing", "miss_range"):
+            v = float(getattr(self, name))
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"FreeSpace: {name} must be finite and >= 0, got {v!r}")
+        if self.samples > 1 and not float(self.spacing) > 0.0:
+            raise ValueError(f"FreeSpace: spacing must be > 0 with more than one sample, got {self.spacing!r}")
+
+    @property
+    def lengths(self) -> np.ndarray:
+        """{gap, spacing, miss_range} as fsdf_set_free_space takes them."""
+        return np.array([self.gap, self.spacing, self.miss_range], np.float64)
+
+
+def free_space_points(depth, sensor_rays, tform: Transform | None, near: float = 0.0, far: float = np.inf,
+                      scale: float = 1.0, kind: str = "range", free_space: FreeSpace | None = None):
+    """The cloud of a depth image with its free-space samples -> (points [n, 3],
+    pixels [n]): the numpy twin of fsdf_set_depth_* under fsdf_set_free_space
+    (csrc/depth.hip), the same bits. The first n_surface = (number of valid
+    pixels) rows are depth_points'; then, with J = free_space.samples and m
+    sending pixels, sample j of the r-th sending pixel (row-major) at row
+    n_surface + (j − 1) · m + r. Per pixel on the stride grid, in this
+    operation order (explicit column arithmetic, as depth_points):
+      L = s − gap (valid) | miss_range (a miss: not valid and not
+          (s > 0 and s < near), when miss_range > 0) | the pixel sends nothing
+      sends iff L − float64(J − 1) · spacing > 0
+      t = L − float64(j − 1) · spacing; c = (t u_x, t u_y, t u_z)
+      p_k = ((R_k0 c_x + R_k1 c_y) + R_k2 c_z) + t_k
+    free_space None: depth_points."""
+    points, pixels = depth_points(depth, sensor_rays, tform, near, far, scale, kind)
+    if free_space is None:
+        return points, pixels
+    fs = free_space
+    d = np.asarray(depth)
+    rays = np.asarray(sensor_rays, np.float64)
+    rows, cols = rays.shape[:2]
+    u = pixel_directions(sensor_rays, kind)
+    near, far, scale = np.float64(near), np.float64(far), np.float64(scale)
+    gap, spacing, miss = np.float64(fs.gap), np.float64(fs.spacing), np.float64(fs.miss_range)
+    J = int(fs.samples)
+    R = np.eye(3) if tform is None else np.asarray(tform.R, np.float64)
+    t = np.zeros(3) if tform is None else np.asarray(tform.t, np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = scale * d.reshape(-1).astype(np.float64)
+        valid = np.isfinite(s) & (s > 0.0) & (s >= near) & (s <= far)
+        too_near = (s > 0.0) & (s < near)
+        is_miss = ~valid & ~too_near & (miss > 0.0)
+        L = np.where(valid, s - gap, miss)
+        i = np.arange(rows * cols)
+        grid = ((i // cols) % fs.stride == 0) & ((i % cols) % fs.stride == 0)
+        sends = grid & (valid | is_miss) & (L - np.float64(J - 1) * spacing > 0.0)
+    send_pix = np.flatnonzero(sends).astype(np.int32)
+    m = len(send_pix)
+    L, us = L[sends], u[sends]
+    out = np.empty((len(points) + J * m, 3), np.float64)
+    out[:len(points)] = points
+    for j in range(J):
+        tt = L - np.float64(j) * spacing
+        cx, cy, cz = tt * us[:, 0], tt * us[:, 1], tt * us[:, 2]
+        blk = out[len(points) + j * m: len(points) + (j + 1) * m]
+        for k in range(3):
+            blk[:, k] = ((R[k, 0] * cx + R[k, 1] * cy) + R[k, 2] * cz) + t[k]
+    return out, np.concatenate([pixels] + [send_pix] * J).astype(np.int32)
+
+
 @dataclass
 class DepthFrame:
     """One frame of a depth camera as it arrives: the image over a DepthSensor's
@@ -147,10 +239,19 @@ class DepthFrame:
     far: float = np.inf
     scale: float = 1.0
     kind: str = "range"
+    free_space: FreeSpace | None = None  # free-space samples after the observed points (None: none)
 
     def points(self):
-        """(points [n, 3], pixels [n]) by depth_points: the resident cloud's bits."""
-        return depth_points(self.depth, self.sensor.rays, self.tform, self.near, self.far, self.scale, self.kind)
+        """(points [n, 3], pixels [n]) by depth_points — with free_space set by
+        free_space_points: the observed points followed by the samples —, the
+        resident cloud's bits."""
+        return free_space_points(self.depth, self.sensor.rays, self.tform, self.near, self.far, self.scale, self.kind,
+                                 self.free_space)
+
+    def n_surface(self) -> int:
+        """The number of observed points (valid pixels): the samples follow them."""
+        return len(depth_points(self.depth, self.sensor.rays, self.tform, self.near, self.far, self.scale,
+                                self.kind)[1])
 
 
 def depth_noise_weights(points, origin, axis, sigma0: float = 0.0012, k: float = 0.0019, z0: float = 0.4):

@@ -115,7 +115,11 @@ class CostFunctor:
     be a depthsensors.DepthFrame: the depth image is uploaded and the device
     forms the cloud (Context.set_depth); `sensed_points` then forms the host
     copy (frame.points()) only when it is read, `n_points` is the cloud's size
-    either way and `depth_pixels()` names each point's pixel."""
+    either way and `depth_pixels()` names each point's pixel. A frame with
+    `free_space` set sends free-space samples after the observed points
+    (fsdf_set_free_space): `n_surface` is the number of observed points,
+    `n_points` counts the samples too, and the objective penalises a sample
+    only where the model covers it (include/flashsdf.h "free space")."""
 
     def __init__(self, manipulator: Manipulator, sensed_points, device: int = 0, precision: int = 64,
                  deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False, loss=None):
@@ -185,8 +189,14 @@ class CostFunctor:
                 self.ctx._sensor_of = None
                 self.ctx.set_sensor(f.sensor.rays, f.kind)
                 self.ctx._sensor_of = (f.sensor, f.kind)
+            self.ctx.set_free_space(getattr(f, "free_space", None))  # (a context setting: this frame's)
             self.ctx.set_depth(f.depth, f.tform, f.near, f.far, f.scale)
         self.n_points = self.ctx.n
+        # n_surface: the first n_surface sensed points are surface observations, the rest free-space
+        # samples (a frame with free_space: the library set the split itself; a plain cloud: none
+        # until set_free_split)
+        split = self.ctx.get_free_split()
+        self.n_surface = self.n_points if split is None else split
 
     def depth_pixels(self):
         """Of a DepthFrame: pixel (row · cols + col) of every sensed point, in
@@ -215,6 +225,25 @@ class CostFunctor:
         self._ensure_resident()
         self.ctx.set_point_weights(weights)  # (refused: the earlier weights stay, here too)
         self.point_weights = weights
+
+    def set_free_split(self, n_surface):
+        """Of a plain cloud whose tail the caller filled with free-space
+        samples of their own: sensed points [n_surface, n) are positions known
+        to be empty and count only where the model covers them (d* < 0) —
+        Σ_surface ρ(d*) + Σ_free [d* < 0] ρ(d*), its gradient and Gauss-Newton
+        Hessian (fsdf_set_free_split; the robust reduction, also without a
+        loss). None or n clears it. Native rigid scenes only. It belongs to
+        the sensed cloud: set_sensed_points drops it (a DepthFrame with
+        free_space sets its own)."""
+        n = self.n_points if n_surface is None else int(n_surface)
+        if n != self.n_points:
+            if not (self._native and self.rigid):
+                raise NotImplementedError("free split: it serves native rigid scenes (no RBF skin, no deformation)")
+            if not 0 <= n <= self.n_points:
+                raise ValueError(f"free split: n_surface {n} of {self.n_points} sensed points")
+        self._ensure_resident()
+        self.ctx.set_free_split(n)
+        self.n_surface = n
 
     def set_loss(self, loss):
         """The robust point loss of this functor's objective (flash.robust;
@@ -255,7 +284,7 @@ class CostFunctor:
         if pre is not None and sensed_points is src:  # (the object prefetched: its device copy)
             self.sensed_points = pre
             self.ctx.set_points_prefetched()
-            self.n_points = self.ctx.n
+            self.n_points = self.n_surface = self.ctx.n
         else:
             self._take(sensed_points)
             self._upload()
@@ -280,7 +309,11 @@ class CostFunctor:
 
     def _ensure_resident(self):
         if getattr(self.manipulator, "_resident_cloud", None) != self._resident:
+            split = getattr(self, "n_surface", None) if self._frame is None else None
             self._upload()
+            if split is not None and split != self.n_points:  # (a plain cloud's split left with the cloud)
+                self.ctx.set_free_split(split)
+                self.n_surface = split
             self.manipulator._resident_cloud = self._resident
             if getattr(self, "point_weights", None) is not None:  # (they left with the cloud)
                 self.ctx.set_point_weights(self.point_weights)
@@ -294,7 +327,8 @@ class CostFunctor:
         return c + _regularizer(self.state, self.weight), accum, extras
 
     def __call__(self, x) -> float:
-        if self.loss is not None or self.point_weights is not None:  # (the robust / weighted objective: the native iteration's cost)
+        if self.loss is not None or self.point_weights is not None or self.n_surface != self.n_points:
+            # (the robust / weighted / split objective: the native iteration's cost)
             return self.value_and_gradient(x)[0]
         return self._pass(x)[0]
 

@@ -103,7 +103,7 @@ def parse(spec):
     return kinds[name](float(scale))
 
 
-def weighted_sums(points, kstar, d, grad, n_surfaces, loss=None, weights=None):
+def weighted_sums(points, kstar, d, grad, n_surfaces, loss=None, weights=None, one_sided=None):
     """The per-surface sums of the (weighted) robust objective in plain numpy,
     from per-point outputs (include/flashsdf.h "per-point confidence
     weights"): with a = weights (None: 1), w = w(d) and ρ of `loss` (None:
@@ -113,17 +113,29 @@ def weighted_sums(points, kstar, d, grad, n_surfaces, loss=None, weights=None):
         (upper triangle, row-major);  W [S] Σ aw.
     The per-point factors are formed as csrc/robust.hip forms them (one product
     aw, wrench scale 2 (aw d), a · ρ); the sums are numpy's, in the dtype of `d`
-    (float64 by default; a test may pass numpy.longdouble)."""
+    (float64 by default; a test may pass numpy.longdouble).
+    one_sided: a boolean mask per point, True for a free-space sample
+    (include/flashsdf.h "free space"): such a point counts only where d < 0.
+    The gate is formed as the kernel forms it (csrc/robust_impl.h
+    one_sided_factor): its factor a becomes exactly 0 where the gate is shut,
+    and the weighted arithmetic follows."""
     dd = _residuals(d)
     t = dd.dtype.type
     P, G = np.asarray(points, dd.dtype), np.asarray(grad, dd.dtype)
     k = np.asarray(kstar)
     w = np.ones_like(dd) if loss is None else loss.weight(dd)
     rho = dd * dd if loss is None else loss.rho(dd)
+    a = None
     if weights is not None:
         a = np.asarray(weights, dd.dtype)
         if a.shape != dd.shape:
             raise ValueError(f"weighted_sums: {a.shape} weights for {dd.shape} points")
+    if one_sided is not None:
+        free = np.asarray(one_sided)
+        if free.dtype != np.bool_ or free.shape != dd.shape:
+            raise ValueError(f"weighted_sums: one_sided is a boolean mask per point, got {free.dtype} {free.shape}")
+        a = np.where(~free | (dd < 0), np.ones_like(dd) if a is None else a, t(0))
+    if a is not None:
         w, rho = a * w, a * rho
     v = np.concatenate([G, np.cross(P, G)], axis=1)
     term = v * (t(2) * (w * dd))[:, None]

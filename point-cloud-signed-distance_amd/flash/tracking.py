@@ -290,7 +290,12 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
     sensed_points may be a depthsensors.DepthFrame (the depth image, the
     sensor and its pose): the device forms the cloud (fsdf_set_depth_*), N is
     the number of valid pixels, and the host forms the points only for a
-    weights callable."""
+    weights callable. A frame with free_space set (depthsensors.FreeSpace)
+    needs no further argument: its samples follow the observed points, the
+    objective penalises a sample only where the model covers it, and N in c / N
+    is the resident point count, samples included (weights: one per resident
+    point, samples included — CostFunctor.depth_pixels names every point's
+    pixel)."""
     solver = solver or _default_solver(manipulator)
     if isinstance(sensed_points, DepthFrame):
         cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision)
@@ -337,7 +342,9 @@ class Tracker:
         the frame's cloud is resident, prefetched or not.
         sensed_points may be a depthsensors.DepthFrame: its image is made
         resident by the device ingest (never prefetched), and the host forms
-        its points only for a weights callable."""
+        its points only for a weights callable. With the frame's free_space set
+        the cloud holds its free-space samples after the observed points; N in
+        c / N is the resident point count, samples included."""
         if isinstance(sensed_points, DepthFrame):
             pts = lambda: self.cost.sensed_points  # noqa: E731 (formed when asked for)
         else:
@@ -368,7 +375,9 @@ def track(manipulator: Manipulator, frames, state: ManipulatorState | None = Non
     """for event in log: gradient_descent!(state, model, sensed_points)
     (examples/irb_and_squishable.ipynb cells 11-12). `frames` yields sensed
     clouds ([n,3]) or depthsensors.DepthFrames (made resident by the device
-    ingest, not prefetched); returns (the per-frame solutions [F, n_states], the Tracker).
+    ingest, not prefetched; a frame's free_space adds its free-space samples, and
+    N in c / N is then the resident point count, samples included); returns (the
+    per-frame solutions [F, n_states], the Tracker).
     loss: a robust point loss for every frame (flash.robust).
     weights: a callable points -> weights applied to every frame (or one array,
     where every frame has as many points)."""
