@@ -748,6 +748,47 @@ int fsdf_set_lm_skins(fsdf_ctx* ctx, int32_t enable);
 int fsdf_eval_skin_moments(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out,
                            double* moments_out);
 
+/* ---- robust objectives on skins --------------------------------------------------
+ * Robust losses, per-point weights and the free-space split above serve
+ * hull-only rigid scenes. fsdf_set_robust_skins (a context setting like
+ * fsdf_set_lm_skins; enable = 0, the default, leaves every refusal above as it
+ * is — the same status, message and bits) opens them to scenes with RBF skins
+ * and deformations: with enable = 1 the robust objective Σ a ρ(d*) (a loss
+ * other than SQUARE, weights, or a split) is served by
+ * fsdf_value_and_gradient and the host loop of fsdf_descend, and — with
+ * fsdf_set_lm_skins(1) as well — by fsdf_value_gradient_hessian and the host
+ * loop of fsdf_descend_lm. The required device loops (fsdf_set_solver 2 / 4,
+ * fsdf_set_lm_solver 2), ranged and keyed clouds, and skins of more than 124
+ * centres for the Hessian are refused as before; fsdf_set_solver 1 / 3 and
+ * fsdf_set_lm_solver 1 run the host loop.
+ *
+ * A skin's block of the accumulator is Σ 2 s j(p), j the point's row of
+ * ∂s/∂(w, a, b, c); the robust objective needs Σ 2 (aw d*) j and, for the
+ * Gauss-Newton term, Σ aw j jᵀ, with aw = a · w(d*), w = ρ′/2d, a through the
+ * one-sided gate when a split is set. Both are launches of their own after
+ * the pass (csrc/robust_skin.hip; csrc/skin_moments.hip's factor variant),
+ * from the pass's k* and d* in resident order and the current RBF rows; the
+ * point's factor is formed in fp64 exactly as the hulls' reduction forms it,
+ * and stands in the pass's own arithmetic (the context's precision) where 2s
+ * does — with a ≡ 1 under SQUARE a point's summands are the pass's, only the
+ * order of summation differs. No floating-point atomics: for a given cloud
+ * layout the results are bit-identical from run to run. The regulariser's
+ * 2 · weight on the deformations is not robustified.
+ *
+ * fsdf_eval_robust_skins (needs the switch; fsdf_eval_robust itself keeps
+ * refusing skins): one pass at the rows of the last fsdf_set_rbf_params.
+ * accum_out: fsdf_eval's full layout [1 + 6S + Σ(4n+4)] — the cost Σρ summed
+ * in surface order from 0.0, a hull's robust wrench, a skin surface's six
+ * wrench entries 0.0 (as the pass leaves them), then the skins' robust
+ * blocks. moments_out: NULL or [S][21], a skin surface's row zero.
+ * skin_moments_out: NULL, or the skins' m×m matrices Σ aw j jᵀ in
+ * fsdf_eval_skin_moments' layout. weight_out: NULL or [S], Σ aw. A cloud of
+ * no points gives zeros and launches nothing. */
+int fsdf_set_robust_skins(fsdf_ctx* ctx, int32_t enable);
+int fsdf_get_robust_skins(const fsdf_ctx* ctx, int32_t* enable_out);
+int fsdf_eval_robust_skins(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out,
+                           double* moments_out, double* skin_moments_out, double* weight_out);
+
 /* ---- context ---------------------------------------------------------------- */
 int fsdf_create(fsdf_ctx** out, const fsdf_opts* opts);
 int fsdf_destroy(fsdf_ctx* ctx);

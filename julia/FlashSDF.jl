@@ -368,6 +368,32 @@ function eval_robust(ctx::Context, poses::Vector{Float64})
 end
 
 """
+Serve robust objectives (a loss, point weights, a free-space split) on scenes with RBF skins and
+deformations too (fsdf_set_robust_skins; off by default: such scenes are then refused as before).
+"""
+set_robust_skins!(ctx::Context, enable::Bool) =
+    check(ctx.ptr, ccall((:fsdf_set_robust_skins, lib), Cint, (Ptr{Void}, Int32), ctx.ptr, Int32(enable)),
+          "set_robust_skins")
+
+"""
+eval_robust on a scene with RBF skins (fsdf_eval_robust_skins; needs set_robust_skins!): returns
+(cost Σρ, accumulator in fsdf_eval's full layout — a skin's wrench 0, then the skins' robust blocks
+Σ 2 (aw d*) j —, moments 21 x S with a skin's column zero, weights Σ aw per surface).
+"""
+function eval_robust_skins(ctx::Context, poses::Vector{Float64})
+    S = div(length(poses), 12)
+    accum = zeros(ctx.accum_len)
+    moments = zeros(21, S)
+    weights = zeros(S)
+    c = Ref{Float64}(0)
+    check(ctx.ptr, ccall((:fsdf_eval_robust_skins, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                          Ptr{Float64}),
+                         ctx.ptr, poses, c, accum, moments, C_NULL, weights), "eval_robust_skins")
+    c[], accum, moments, weights
+end
+
+"""
 Per-point confidence weights a_i >= 0 (finite) of the resident cloud, in the order of the points
 given to set_points! (fsdf_set_point_weights): every sum of eval_robust carries a_i as a factor
 of point i's terms (cost Σ a ρ, wrench Σ 2 a w d* v, moments Σ a w v vᵀ). They belong to the

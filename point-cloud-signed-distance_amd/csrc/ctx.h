@@ -180,7 +180,13 @@ struct fsdf_ctx {
   double loss_scale = 0.0;
   fsdf::DevBuf<double> robust_partials, robust_rows;
   fsdf::PinnedBuf<double> h_robust;
-  std::vector<double> robust_accum, robust_moments;  // the accumulator [1 + 6S] and moments [S][21] from the rows
+  std::vector<double> robust_accum, robust_moments;  // the accumulator (fsdf_eval's layout) and moments [S][21] from the rows
+  // robust objectives on RBF skins and deformations (fsdf_set_robust_skins: a context setting like
+  // lm_skins; robust_skin.hip): the workgroups' partials, the skins' blocks [rbf_acc], their pinned
+  // read-back. The weighted skin moments reuse skin_partials / skin_moments / h_skin_moments.
+  int robust_skins = 0;
+  fsdf::DevBuf<double> robust_skin_partials, robust_skin_blocks;
+  fsdf::PinnedBuf<double> h_robust_skin;
   // per-point confidence weights (fsdf_set_point_weights; point_weights.hip): they belong to the
   // resident cloud (every new one clears them). conf_src [n] in the caller's order, conf_res [n]
   // in resident order (sorted clouds: gathered through cur.perm; conf_stale: the layout changed
@@ -294,9 +300,11 @@ int ensure_host_acc(fsdf_ctx* c, int len);
 enum { kMomentsRigid = 0, kMomentsAll = 1, kMomentsSkins = 2 };
 int run_pass_moments(fsdf_ctx* c, const double* poses, const char* who, int what = kMomentsRigid);
 // (the pass with k*, d*, ∇d* in resident order, then the robust launch: the rows [S][29] (moments)
-// or [S][8] to h_robust, in flight; hull-only scenes. robust_rows_finish, after the
-// synchronisation: robust_accum (fsdf_eval's layout, Σρ summed in surface order) and — moments —
-// robust_moments from the rows)
+// or [S][8] to h_robust, in flight; hull-only scenes — with fsdf_set_robust_skins also scenes with
+// RBF skins and deformations: the skins' blocks (robust_skin.hip) to h_robust_skin and — moments —
+// their weighted second moments to h_skin_moments. robust_rows_finish, after the
+// synchronisation: robust_accum (fsdf_eval's layout, Σρ summed in surface order, a skin's wrench
+// 0.0, then the skins' blocks) and — moments — robust_moments from the rows (a skin's row zero))
 int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool moments);
 void robust_rows_finish(fsdf_ctx* c, bool moments);
 // point_weights.hip: the weights in resident order for a robust launch (null: none set), regathered

@@ -303,6 +303,19 @@ hipError_t launch_robust(int precision, bool moments, const void* d_pts, const i
                          const double* d_grad, const double* d_conf, const int32_t* d_perm, int64_t n_surface,
                          int64_t n, int S, int kind, double scale, double* d_partials, double* d_rows,
                          hipStream_t s);
+// ---- the RBF skins' blocks under a robust objective (robust_skin.hip) -----------
+// d_blocks [lm.rbf_acc]: per skin r its block of the accumulator, Σ t j(p) over
+// the resident points with k* = r's surface — rbf_adjoint's sums with the
+// point's t = 2 (aw d*) (robust_impl.h wrench_scale, fp64, from the pass's d* in
+// resident order) where the pass has 2s. The grid and the runs are
+// launch_robust's (robust_groups, robust_run: functions of n alone), four waves
+// per workgroup; d_conf, d_perm, n_surface as launch_robust's. d_rows: the RBF
+// rows of the context precision (PosedModel::rbf_rows). n > 0, lm.R >= 1.
+size_t robust_skin_partials_len(int64_t n, int rbf_acc);  // doubles of d_partials
+hipError_t launch_robust_skin(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_d,
+                              const void* d_rows, const LocalModel& lm, const double* d_conf, const int32_t* d_perm,
+                              int64_t n_surface, int64_t n, int kind, double scale, double* d_partials,
+                              double* d_blocks, hipStream_t s);
 // res[i] = src[perm[i]] over n doubles (point_weights.hip: a per-point side array
 // into resident order; an index outside [0, n) reads as 0)
 hipError_t launch_gather_f64(const double* d_src, const int32_t* d_perm, int64_t n, double* d_res, hipStream_t s);
@@ -379,6 +392,13 @@ size_t skin_moments_partials_len(int64_t n, int U);  // doubles of d_partials
 hipError_t launch_skin_moments(int precision, const void* d_pts, const int32_t* d_kstar, const void* d_rows, int64_t n,
                                const SkinPlan& plan, double* d_partials, double* d_moments, hipStream_t s,
                                const int* skip = nullptr);
+// the same with a factor per point, M_r = Σ aw j jᵀ (a robust objective's IRLS
+// term): aw = a · w(d*) from d_d (the pass's d* in resident order), the loss,
+// d_conf, d_perm and n_surface as launch_robust's, formed in fp64
+hipError_t launch_skin_moments_weighted(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_d,
+                                        const void* d_rows, const double* d_conf, const int32_t* d_perm,
+                                        int64_t n_surface, int kind, double scale, int64_t n, const SkinPlan& plan,
+                                        double* d_partials, double* d_moments, hipStream_t s);
 
 hipError_t launch_to_f32(const double* src, float* dst, int64_t count, hipStream_t s);
 

@@ -255,6 +255,40 @@ double g_host_t[8];  // (ctx.h: the host loop's clocks, printed by fsdf_descend)
 long g_host_n;
 #endif
 
+// The Gauss-Newton matrix of a scene with skins and deformations (fsdf_set_lm_skins), from the hulls'
+// moments hm [S][21] (a skin's row zero) and the skins' second moments sm: A = A_hulls in the nq
+// block + Σ_r L_r M_r L_rᵀ over the nx = nq + 3 n_deform coordinates, H = 2 A + 2 weight I on the
+// deformations (the regulariser is a sum of squares too, and is not robustified)
+static int skins_hessian(fsdf_ctx* c, const double* x, const double* hm, const double* sm, double* hess_out,
+                         const char* who) {
+  auto& M = c->mech;
+  const int nq = M.nq, nx = nq + 3 * M.n_deform, S = c->lm.S;
+  M.gn_work.resize((size_t)36 * M.nb + (size_t)6 * nq);
+  M.gn_hull.resize((size_t)nq * nq);
+  int rc = fsdf_gauss_newton_matrix(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.Rb.data(),
+                                    M.tb.data(), x, S, M.surface_body.data(), hm, nq, M.gn_work.data(),
+                                    M.gn_hull.data());
+  if (rc) return fail(c, rc, "%s: Gauss-Newton matrix", who);
+  for (size_t i = 0; i < (size_t)nx * nx; ++i) hess_out[i] = 0.0;
+  for (int i = 0; i < nq; ++i)
+    for (int j = 0; j < nq; ++j) hess_out[(size_t)i * nx + j] = M.gn_hull[(size_t)i * nq + j];
+  for (auto& D : M.rbf) {
+    const int m = 4 * D.n + 4;
+    M.skin_L.resize((size_t)nx * m);
+    M.skin_work.resize(std::max((size_t)8 * D.n + 8 + (size_t)12 * M.nb + nx, (size_t)nx * m));
+    rc = fsdf_rbf_state_map(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.R.data(),
+                            M.Rb.data(), M.tb.data(), x, nq, D.n, D.centres.data(), D.u.data(), D.lu.data(),
+                            D.piv.data(), D.body.data(), D.drow.data(), M.n_deform, M.skin_work.data(),
+                            M.skin_L.data());
+    if (!rc) rc = fsdf_gauss_newton_add(nx, m, M.skin_L.data(), sm, M.skin_work.data(), hess_out);
+    if (rc) return fail(c, rc, "%s: the skins' Gauss-Newton term", who);
+    sm += (size_t)m * m;
+  }
+  for (size_t i = 0; i < (size_t)nx * nx; ++i) hess_out[i] = 2.0 * hess_out[i];
+  for (int i = nq; i < nx; ++i) hess_out[(size_t)i * nx + i] += 2.0 * M.weight;
+  return FSDF_OK;
+}
+
 // With a loss other than SQUARE set (fsdf_set_loss), per-point weights
 // (fsdf_set_point_weights) or a free-space split (fsdf_set_free_split; both
 // also under SQUARE): the same iteration on the
@@ -262,14 +296,22 @@ long g_host_n;
 // robust launch (robust.hip) in place of the pass's own sums, and the same
 // chain rule on the accumulator assembled from its rows. The auto regroup is
 // queued after the robust launch: it reads the layout the pass ran on. Rigid
-// scenes only. hess_out null: the rows without the moments (the same (c, g) bits).
+// scenes only — with fsdf_set_robust_skins scenes with RBF skins and deformations too: the skins'
+// blocks come from robust_skin.hip, the Hessian (fsdf_set_lm_skins as well) from the robust hull
+// moments and the weighted skin moments through the non-rigid branch's own arithmetic.
+// hess_out null: the rows without the moments (the same (c, g) bits).
 static int robust_iteration(fsdf_ctx* c, const double* x, double* cost_out, double* grad_out, double* hess_out,
                             const char* who) {
-  if (c->lm.R > 0 || c->mech.n_deform > 0)
+  const bool rigid = c->lm.R == 0 && c->mech.n_deform == 0;
+  if (!rigid && !c->robust_skins)
     return fail(c, FSDF_ERR_STATE,
                 "%s: the loss set by fsdf_set_loss (kind %d)%s%s serves rigid scenes (no RBF skin, no deformation)", who,
                 c->loss_kind, c->conf_set ? " and the weights of fsdf_set_point_weights" : "",
                 c->free_split >= 0 ? " and the free-space split of fsdf_set_free_split" : "");
+  if (!rigid && hess_out && !c->lm_skins)
+    return fail(c, FSDF_ERR_STATE,
+                "%s: the Gauss-Newton matrix is defined for rigid scenes (no RBF skin, no deformation); "
+                "fsdf_set_lm_skins serves the others", who);
   int rc = iteration_prepare(c, x, who);
   if (rc) return rc;
   auto& M = c->mech;
@@ -282,6 +324,8 @@ static int robust_iteration(fsdf_ctx* c, const double* x, double* cost_out, doub
   robust_rows_finish(c, moments);
   rc = iteration_finish(c, x, c->robust_accum.data(), cost_out, grad_out, who);
   if (rc || !moments) return rc;
+  if (!rigid)  // (robust_moments: a skin's row zero; h_skin_moments: Σ aw j jᵀ, or untouched with no skin)
+    return skins_hessian(c, x, c->robust_moments.data(), c->h_skin_moments.get(), hess_out, who);
   const int nq = M.nq;
   M.gn_work.resize((size_t)36 * M.nb + (size_t)6 * nq);
   rc = fsdf_gauss_newton_matrix(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.Rb.data(),
@@ -369,37 +413,12 @@ extern "C" int fsdf_value_gradient_hessian(fsdf_ctx* c, const double* x, double*
     for (size_t i = 0; i < (size_t)nq * nq; ++i) hess_out[i] = 2.0 * hess_out[i];
     return FSDF_OK;
   }
-  // skins and deformations (fsdf_set_lm_skins): A = A_hulls in the nq block +
-  // Σ_r L_r M_r L_rᵀ over the nx = nq + 3 n_deform coordinates, H = 2 A +
-  // 2 weight I on the deformations (the regulariser is a sum of squares too)
-  const int nx = nq + 3 * M.n_deform, S = c->lm.S;
+  // skins and deformations (fsdf_set_lm_skins)
   double* hm = c->h_moments.get();
-  for (int k = 0; k < S; ++k)  // (a skin's points have no hull moments)
+  for (int k = 0; k < c->lm.S; ++k)  // (a skin's points have no hull moments)
     if (c->h_surface_kind[k] != FSDF_SURFACE_HULL)
       for (int e = 0; e < fsdf::kMomentsLen; ++e) hm[(size_t)fsdf::kMomentsLen * k + e] = 0.0;
-  M.gn_hull.resize((size_t)nq * nq);
-  rc = fsdf_gauss_newton_matrix(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.Rb.data(),
-                                M.tb.data(), x, S, M.surface_body.data(), hm, nq, M.gn_work.data(), M.gn_hull.data());
-  if (rc) return fail(c, rc, "value_gradient_hessian: Gauss-Newton matrix");
-  for (size_t i = 0; i < (size_t)nx * nx; ++i) hess_out[i] = 0.0;
-  for (int i = 0; i < nq; ++i)
-    for (int j = 0; j < nq; ++j) hess_out[(size_t)i * nx + j] = M.gn_hull[(size_t)i * nq + j];
-  const double* sm = c->h_skin_moments.get();
-  for (auto& D : M.rbf) {
-    const int m = 4 * D.n + 4;
-    M.skin_L.resize((size_t)nx * m);
-    M.skin_work.resize(std::max((size_t)8 * D.n + 8 + (size_t)12 * M.nb + nx, (size_t)nx * m));
-    rc = fsdf_rbf_state_map(M.nb, M.parent.data(), M.kind.data(), M.qoff.data(), M.axis.data(), M.R.data(),
-                            M.Rb.data(), M.tb.data(), x, nq, D.n, D.centres.data(), D.u.data(), D.lu.data(),
-                            D.piv.data(), D.body.data(), D.drow.data(), M.n_deform, M.skin_work.data(),
-                            M.skin_L.data());
-    if (!rc) rc = fsdf_gauss_newton_add(nx, m, M.skin_L.data(), sm, M.skin_work.data(), hess_out);
-    if (rc) return fail(c, rc, "value_gradient_hessian: the skins' Gauss-Newton term");
-    sm += (size_t)m * m;
-  }
-  for (size_t i = 0; i < (size_t)nx * nx; ++i) hess_out[i] = 2.0 * hess_out[i];
-  for (int i = nq; i < nx; ++i) hess_out[(size_t)i * nx + i] += 2.0 * M.weight;
-  return FSDF_OK;
+  return skins_hessian(c, x, hm, c->h_skin_moments.get(), hess_out, "value_gradient_hessian");
 }
 
 

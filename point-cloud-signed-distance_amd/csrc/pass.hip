@@ -3,7 +3,8 @@
 // outputs and their read-back, fsdf_eval / fsdf_eval_device, the permutation
 // getters, and the pass followed by the second-moments reduction
 // (run_pass_moments, fsdf_eval_moments) or by the sums of a robust point loss
-// (fsdf_set_loss, run_pass_robust, fsdf_eval_robust).
+// (fsdf_set_loss, run_pass_robust, fsdf_eval_robust; on scenes with RBF skins
+// behind fsdf_set_robust_skins, fsdf_eval_robust_skins).
 
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -512,11 +513,21 @@ extern "C" int fsdf_get_loss(const fsdf_ctx* c, int32_t* kind_out, double* scale
 // with the locals. A cloud of no points launches no robust kernel: zero rows.
 // The pass's own least-squares accumulator goes to the context's device
 // accumulator and is not read.
+// With fsdf_set_robust_skins, scenes with RBF skins and deformations too: robust_kernel gives Σρ, Σw and
+// the hull surfaces' wrenches and moments for every k*; the skins' blocks come from a launch of
+// their own (robust_skin.hip) into h_robust_skin and — moments — their weighted second moments
+// Σ aw j jᵀ (skin_moments.hip's factor variant) into h_skin_moments, all from the same k*, d* and
+// the rows the pass read.
 int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool moments) {
   const int S = c->lm.S;
-  if (c->lm.R > 0 || c->mech.n_deform > 0)
+  if ((c->lm.R > 0 || c->mech.n_deform > 0) && !c->robust_skins)
     return fail(c, FSDF_ERR_STATE, "%s: a robust loss%s serves hull-only scenes (no RBF skin, no deformation)", who,
                 c->free_split >= 0 ? " or a free-space split (fsdf_set_free_split)" : "");
+  const bool skins = c->lm.R > 0;
+  fsdf::SkinPlan plan;
+  if (skins && moments && !fsdf::skin_moments_plan(S, c->h_surface_kind.data(), c->h_n_centers.data(), &plan))
+    return fail(c, FSDF_ERR_STATE, "%s: the skin moments serve skins of at most %d centres (n + 4 <= 128)", who,
+                fsdf::kSkinMaxCentres);
   if (!fsdf::robust_fit(S))
     return fail(c, FSDF_ERR_STATE,
                 "%s: the robust table of %d surfaces (%zu bytes) does not fit %d bytes of LDS (at most 282 surfaces)",
@@ -529,6 +540,17 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
   HIPCHECK(c, c->robust_partials.reserve(fsdf::robust_partials_len(n, S)));
   HIPCHECK(c, c->robust_rows.reserve((size_t)S * fsdf::kRobustLen));
   HIPCHECK(c, c->h_robust.reserve((size_t)S * fsdf::kRobustLen));
+  const size_t blen = skins ? (size_t)c->lm.rbf_acc : 0, slen = skins && moments ? (size_t)plan.total : 0;
+  if (skins) {
+    HIPCHECK(c, c->robust_skin_partials.reserve(fsdf::robust_skin_partials_len(n, c->lm.rbf_acc)));
+    HIPCHECK(c, c->robust_skin_blocks.reserve(blen));
+    HIPCHECK(c, c->h_robust_skin.reserve(blen));
+  }
+  if (slen) {
+    HIPCHECK(c, c->skin_partials.reserve(fsdf::skin_moments_partials_len(n, plan.U)));
+    HIPCHECK(c, c->skin_moments.reserve(slen));
+    HIPCHECK(c, c->h_skin_moments.reserve(slen));
+  }
   // (2) read the pointers
   const void* d_pts = c->cur.pts.get();
   int32_t* d_kstar = c->kstar.get();
@@ -538,6 +560,12 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
   double* d_rows = c->robust_rows.get();
   double* h_rows = c->h_robust.get();
   double* d_accum = c->model.accum.get();
+  double* d_skin_bpartials = c->robust_skin_partials.get();
+  double* d_skin_blocks = c->robust_skin_blocks.get();
+  double* h_skin_blocks = c->h_robust_skin.get();
+  double* d_skin_partials = c->skin_partials.get();
+  double* d_skin_moments = c->skin_moments.get();
+  double* h_skin_moments = c->h_skin_moments.get();
   // (the per-point weights in resident order, regathered when the layout changed since; null: none set)
   const double* d_conf = nullptr;
   rc = point_weights_resident(c, &d_conf);
@@ -548,6 +576,8 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
   if (n == 0) {
     HIPCHECK(c, hipStreamSynchronize(c->stream));  // (an earlier read-back into the rows)
     memset(h_rows, 0, rlen * sizeof(double));
+    if (skins) memset(h_skin_blocks, 0, blen * sizeof(double));
+    if (slen) memset(h_skin_moments, 0, slen * sizeof(double));
     return FSDF_OK;
   }
   // (a split: the one-sided instantiations, which read the resident→caller permutation — null: the
@@ -555,6 +585,20 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
   HIPCHECK(c, fsdf::launch_robust(c->precision, moments, d_pts, d_kstar, d_d, d_grad, d_conf, c->cur.perm.get(),
                                   c->free_split, n, S, c->loss_kind, c->loss_scale, d_partials, d_rows, c->stream));
   HIPCHECK(c, hipMemcpyAsync(h_rows, d_rows, rlen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (skins) {  // (the rows the pass just read: fsdf_set_rbf_params' last, in order on the stream)
+    HIPCHECK(c, fsdf::launch_robust_skin(c->precision, d_pts, d_kstar, d_d, c->pm.rbf_rows, c->lm, d_conf,
+                                         c->cur.perm.get(), c->free_split, n, c->loss_kind, c->loss_scale,
+                                         d_skin_bpartials, d_skin_blocks, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(h_skin_blocks, d_skin_blocks, blen * sizeof(double), hipMemcpyDeviceToHost,
+                               c->stream));
+  }
+  if (slen) {
+    HIPCHECK(c, fsdf::launch_skin_moments_weighted(c->precision, d_pts, d_kstar, d_d, c->pm.rbf_rows, d_conf,
+                                                   c->cur.perm.get(), c->free_split, c->loss_kind, c->loss_scale, n,
+                                                   plan, d_skin_partials, d_skin_moments, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(h_skin_moments, d_skin_moments, slen * sizeof(double), hipMemcpyDeviceToHost,
+                               c->stream));
+  }
   return FSDF_OK;
 }
 
@@ -563,19 +607,26 @@ int run_pass_robust(fsdf_ctx* c, const double* poses, const char* who, bool mome
 void robust_rows_finish(fsdf_ctx* c, bool moments) {
   const int S = c->lm.S, len = moments ? fsdf::kRobustLen : fsdf::kRobustTail, m0 = len - fsdf::kRobustTail;
   const double* rows = c->h_robust.get();
-  c->robust_accum.assign((size_t)1 + 6 * (size_t)S, 0.0);
+  // (a rigid scene's accumulator is [1 + 6S]; a skin's wrench stays 0.0, as the pass leaves it)
+  c->robust_accum.assign((size_t)accum_len(c), 0.0);
   double cost = 0.0;
   for (int k = 0; k < S; ++k) {
     const double* r = rows + (size_t)len * k;
     cost += r[m0 + 6];
+    if (c->h_surface_kind[k] != FSDF_SURFACE_HULL) continue;
     for (int i = 0; i < 6; ++i) c->robust_accum[(size_t)1 + 6 * (size_t)k + i] = r[m0 + i];
   }
   c->robust_accum[0] = cost;
+  if (c->lm.R > 0)
+    memcpy(c->robust_accum.data() + 1 + 6 * (size_t)S, c->h_robust_skin.get(), (size_t)c->lm.rbf_acc * sizeof(double));
   if (moments) {
     c->robust_moments.resize((size_t)S * fsdf::kMomentsLen);
     for (int k = 0; k < S; ++k)
-      memcpy(c->robust_moments.data() + (size_t)fsdf::kMomentsLen * k, rows + (size_t)len * k,
-             fsdf::kMomentsLen * sizeof(double));
+      if (c->h_surface_kind[k] == FSDF_SURFACE_HULL)
+        memcpy(c->robust_moments.data() + (size_t)fsdf::kMomentsLen * k, rows + (size_t)len * k,
+               fsdf::kMomentsLen * sizeof(double));
+      else  // (a skin's points have no hull moments)
+        memset(c->robust_moments.data() + (size_t)fsdf::kMomentsLen * k, 0, fsdf::kMomentsLen * sizeof(double));
   }
 }
 
@@ -597,6 +648,48 @@ extern "C" int fsdf_eval_robust(fsdf_ctx* c, const double* poses, double* cost_o
   if (cost_out) *cost_out = c->robust_accum[0];
   if (accum_out) memcpy(accum_out, c->robust_accum.data(), c->robust_accum.size() * sizeof(double));
   if (moments) memcpy(moments_out, c->robust_moments.data(), c->robust_moments.size() * sizeof(double));
+  if (weight_out)
+    for (int k = 0; k < S; ++k) weight_out[k] = c->h_robust.get()[(size_t)len * k + len - 1];
+  return FSDF_OK;
+}
+
+// ---- robust objectives on RBF skins and deformations (robust_skin.hip) --------------------
+extern "C" int fsdf_set_robust_skins(fsdf_ctx* c, int32_t enable) {
+  if (!c) return FSDF_ERR_ARG;
+  if (enable != 0 && enable != 1) return fail(c, FSDF_ERR_ARG, "set_robust_skins: enable %d", enable);
+  c->robust_skins = enable;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_get_robust_skins(const fsdf_ctx* c, int32_t* enable_out) {
+  if (!c || !enable_out) return FSDF_ERR_ARG;
+  *enable_out = c->robust_skins;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_eval_robust_skins(fsdf_ctx* c, const double* poses, double* cost_out, double* accum_out,
+                                      double* moments_out, double* skin_moments_out, double* weight_out) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval_robust_skins: no model (call fsdf_set_surfaces first)");
+  if (!poses) return fail(c, FSDF_ERR_ARG, "eval_robust_skins: poses required");
+  if (!c->robust_skins)
+    return fail(c, FSDF_ERR_STATE, "eval_robust_skins: robust objectives on skins are off (fsdf_set_robust_skins)");
+  HIPCHECK(c, hipSetDevice(c->device));
+  const bool moments = moments_out != nullptr || skin_moments_out != nullptr;
+  const int rc = run_pass_robust(c, poses, "eval_robust_skins", moments);
+  if (rc) return rc;
+  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  robust_rows_finish(c, moments);
+  const int S = c->lm.S, len = moments ? fsdf::kRobustLen : fsdf::kRobustTail;
+  if (cost_out) *cost_out = c->robust_accum[0];
+  if (accum_out) memcpy(accum_out, c->robust_accum.data(), c->robust_accum.size() * sizeof(double));
+  if (moments_out) memcpy(moments_out, c->robust_moments.data(), c->robust_moments.size() * sizeof(double));
+  if (skin_moments_out && c->lm.R > 0) {
+    size_t total = 0;
+    for (int k = 0; k < S; ++k)
+      if (c->h_n_centers[k] > 0) total += (size_t)(4 * c->h_n_centers[k] + 4) * (size_t)(4 * c->h_n_centers[k] + 4);
+    memcpy(skin_moments_out, c->h_skin_moments.get(), total * sizeof(double));
+  }
   if (weight_out)
     for (int k = 0; k < S; ++k) weight_out[k] = c->h_robust.get()[(size_t)len * k + len - 1];
   return FSDF_OK;

@@ -1,7 +1,8 @@
 // rbf_sdf.h — RBF interpolating skins in the pass kernels: the field, the
 // skin's signed distance, the adjoint sums of the lanes nearest to a skin.
-// sdf_kernels.hip includes it (through scene_eval.h), and skin_moments.hip
-// for the field's types and rbf_skin_from_field.
+// sdf_kernels.hip includes it (through scene_eval.h), skin_moments.hip for
+// the field's types and rbf_skin_from_field, and robust_skin.hip for
+// rbf_adjoint with a robust factor in place of 2s.
 #pragma once
 #include "sdf_device_math.h"
 
@@ -80,15 +81,19 @@ __device__ __forceinline__ void rbf_skin_from_field(const RbfField<T>& F, T& s, 
 // (sel): per centre λ_w_i = Σ 2s ∂s/∂w_i and E_i = Σ 2s ∂s/∂c_i (coefficients
 // fixed), then λ_a, λ_b — wave-summed, added by lane 0 into acc (LDS):
 //   acc[0..n) = λ_w, acc[n] = λ_a, acc[n+1..n+4) = λ_b, acc[n+4+3i..] = E_i.
-template <typename T>
+// SCALED (robust_skin.hip): the lane's `scale` stands where 2s does — the
+// robust factor 2 (aw d*) of a weighted or robust objective; the pass's own
+// instantiation (SCALED = false) never reads it.
+template <typename T, bool SCALED = false>
 __device__ __forceinline__ void rbf_adjoint(T px, T py, T pz, const T* __restrict__ rows, int nc,
-                                            T* __restrict__ lw, int cap, bool sel, double* __restrict__ acc) {
+                                            T* __restrict__ lw, int cap, bool sel, double* __restrict__ acc,
+                                            T scale = (T)0) {
   typedef typename Row4<T>::type R4;
   RbfField<T> F;
   rbf_field(px, py, pz, rows, nc, lw, cap, F);
   T s, sgx, sgy, sgz, c, invG;
   rbf_skin_from_field(F, s, sgx, sgy, sgz, c, invG);
-  const T two_s = (T)2 * s;
+  const T two_s = SCALED ? scale : (T)2 * s;
   const T dsdf = invG;
   const T ux = -c * F.gx, uy = -c * F.gy, uz = -c * F.gz;  // ∂s/∂∇f
   const int lane = threadIdx.x & 63;

@@ -33,6 +33,7 @@
 
 #include "fsdf_internal.h"
 #include "rbf_sdf.h"
+#include "robust_impl.h"
 
 namespace fsdf {
 
@@ -94,14 +95,28 @@ __device__ __forceinline__ void skin_unit_pair(int u, int nbk, int& bi, int& bj)
   bj = bi + u;
 }
 
-template <typename T, bool MFMA>
-__global__ __launch_bounds__(kSkinBlock) void skin_moments_kernel(const T* __restrict__ pts,
-                                                                  const int32_t* __restrict__ kstar,
-                                                                  const T* __restrict__ rows_g, int64_t N, int n,
-                                                                  int surf, int groups, int run,
-                                                                  double* __restrict__ partials,
-                                                                  const int* __restrict__ skip) {
-  if (skip && *skip) return;  // (uniform: a finished device LM frame)
+// FACTOR (skin_moments_factor_kernel): what a point's factor aw = a · w(d*) of a robust
+// objective is formed from — the pass's d* in resident order, the loss, the weights in
+// resident order (null: none), the resident→caller permutation (null: the caller's
+// order) and n_surface (< 0: no split), as robust_kernel reads them
+struct SkinFactor {
+  const double* dstar = nullptr;
+  const double* conf = nullptr;
+  const int32_t* perm = nullptr;
+  int64_t n_surface = -1;
+  int kind = 0;
+  double scale = 0.0;
+};
+
+// the body of both kernels. FACTOR = false: Σ j jᵀ. FACTOR: Σ aw j jᵀ — aw is formed in fp64
+// where the point's field is, travels in the selection slot pd[7] of its staged record
+// (aw = 0: the point contributes nothing, as a point of another surface) and scales the
+// A operand of the rank update
+template <typename T, bool MFMA, bool FACTOR>
+__device__ __forceinline__ void skin_moments_body(const T* __restrict__ pts, const int32_t* __restrict__ kstar,
+                                                  const T* __restrict__ rows_g, int64_t N, int n, int surf,
+                                                  int groups, int run, double* __restrict__ partials,
+                                                  const SkinFactor& fac) {
   __shared__ __attribute__((aligned(32))) double s_rows[4 * (kSkinMaxCentres + 1)];  // the skin's rows, widened
   __shared__ __attribute__((aligned(16))) double s_pd[4][64][8];  // per chunk and point: p, 1/|∇f|, ∂s/∂∇f, selected
   __shared__ __attribute__((aligned(32))) double s_J[2][32][kSkinLd];  // a half chunk's columns of blocks bi, bj
@@ -160,7 +175,15 @@ __global__ __launch_bounds__(kSkinBlock) void skin_moments_kernel(const T* __res
         double* pd = s_pd[wave][lane];
         pd[0] = px; pd[1] = py; pd[2] = pz; pd[3] = invG;
         pd[4] = -cc * F.gx; pd[5] = -cc * F.gy; pd[6] = -cc * F.gz;
-        pd[7] = sel ? 1.0 : 0.0;
+        double aw = sel ? 1.0 : 0.0;
+        if (FACTOR && sel) {
+          const double d = fac.dstar[i];
+          double a = fac.conf ? fac.conf[i] : 1.0;
+          if (fac.n_surface >= 0)
+            a = robust::one_sided_factor(robust::free_sample(fac.perm ? (int64_t)fac.perm[i] : i, fac.n_surface), d, a);
+          aw = a * robust::weight(fac.kind, fac.scale, d);
+        }
+        pd[7] = aw;
       }
     }
     __syncthreads();
@@ -207,7 +230,8 @@ __global__ __launch_bounds__(kSkinBlock) void skin_moments_kernel(const T* __res
 #pragma unroll
           for (int t = 0; t < 8; ++t) {
             const int row = 4 * t + (lane >> 4);
-            const double a = JA[row][16 * wave + (lane & 15)];
+            const double a = FACTOR ? JA[row][16 * wave + (lane & 15)] * s_pd[ch][32 * h + row][7]
+                                    : JA[row][16 * wave + (lane & 15)];
 #pragma unroll
             for (int tj = 0; tj < 4; ++tj)
               acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, JB[row][16 * tj + (lane & 15)], acc[tj], 0, 0, 0);
@@ -215,7 +239,7 @@ __global__ __launch_bounds__(kSkinBlock) void skin_moments_kernel(const T* __res
         } else {  // (A/B: thread t owns row t >> 2 of the block, 16 columns)
           const int i = tid >> 2, j0 = 16 * (tid & 3);
           for (int p = 0; p < 32; ++p) {
-            const double a = JA[p][i];
+            const double a = FACTOR ? JA[p][i] * s_pd[ch][32 * h + p][7] : JA[p][i];
 #pragma unroll
             for (int jj = 0; jj < 16; ++jj) facc[jj] = mfma_(a, JB[p][j0 + jj], facc[jj]);
           }
@@ -236,6 +260,27 @@ __global__ __launch_bounds__(kSkinBlock) void skin_moments_kernel(const T* __res
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) out[(tid >> 2) * kSkinTile + 16 * (tid & 3) + jj] = facc[jj];
   }
+}
+
+template <typename T, bool MFMA>
+__global__ __launch_bounds__(kSkinBlock) void skin_moments_kernel(const T* __restrict__ pts,
+                                                                  const int32_t* __restrict__ kstar,
+                                                                  const T* __restrict__ rows_g, int64_t N, int n,
+                                                                  int surf, int groups, int run,
+                                                                  double* __restrict__ partials,
+                                                                  const int* __restrict__ skip) {
+  if (skip && *skip) return;  // (uniform: a finished device LM frame)
+  skin_moments_body<T, MFMA, false>(pts, kstar, rows_g, N, n, surf, groups, run, partials, SkinFactor());
+}
+
+template <typename T, bool MFMA>
+__global__ __launch_bounds__(kSkinBlock) void skin_moments_factor_kernel(const T* __restrict__ pts,
+                                                                         const int32_t* __restrict__ kstar,
+                                                                         const T* __restrict__ rows_g, int64_t N,
+                                                                         int n, int surf, int groups, int run,
+                                                                         double* __restrict__ partials,
+                                                                         SkinFactor fac) {
+  skin_moments_body<T, MFMA, true>(pts, kstar, rows_g, N, n, surf, groups, run, partials, fac);
 }
 
 // the kernel's column q — (w_i, c_i) per centre i = q >> 2, then (a, b) — in the block's order
@@ -264,9 +309,10 @@ __global__ __launch_bounds__(256) void skin_moments_finish_kernel(const double* 
 }
 
 // one pair of launches per skin: its units' workgroups, then the finish
-hipError_t launch_skin_moments(int precision, const void* d_pts, const int32_t* d_kstar, const void* d_rows, int64_t n,
-                               const SkinPlan& plan, double* d_partials, double* d_moments, hipStream_t s,
-                               const int* skip) {
+static hipError_t launch_skin_moments_impl(int precision, const void* d_pts, const int32_t* d_kstar,
+                                           const void* d_rows, int64_t n, const SkinPlan& plan, double* d_partials,
+                                           double* d_moments, hipStream_t s, const int* skip,
+                                           const SkinFactor* fac) {
   if (n <= 0 || plan.U < 1 || plan.U > kSkinMaxUnits || plan.R < 1 || !d_pts || !d_kstar || !d_rows || !d_partials ||
       !d_moments)
     return hipErrorInvalidValue;
@@ -275,7 +321,15 @@ hipError_t launch_skin_moments(int precision, const void* d_pts, const int32_t* 
   for (int r = 0; r < plan.R; ++r) {
     const int units = (r + 1 < plan.R ? plan.unit0[r + 1] : plan.U) - plan.unit0[r];
     double* part = d_partials + (size_t)plan.unit0[r] * groups * kSkinPartial;
-    if (precision == 64)
+    if (fac && precision == 64)
+      hipLaunchKernelGGL((skin_moments_factor_kernel<double, kMfma>), dim3(units * groups), dim3(kSkinBlock), 0, s,
+                         (const double*)d_pts, d_kstar, (const double*)d_rows + 4 * (size_t)plan.row_off[r], n,
+                         plan.n[r], plan.surf[r], groups, run, part, *fac);
+    else if (fac)
+      hipLaunchKernelGGL((skin_moments_factor_kernel<float, kMfma>), dim3(units * groups), dim3(kSkinBlock), 0, s,
+                         (const float*)d_pts, d_kstar, (const float*)d_rows + 4 * (size_t)plan.row_off[r], n,
+                         plan.n[r], plan.surf[r], groups, run, part, *fac);
+    else if (precision == 64)
       hipLaunchKernelGGL((skin_moments_kernel<double, kMfma>), dim3(units * groups), dim3(kSkinBlock), 0, s,
                          (const double*)d_pts, d_kstar, (const double*)d_rows + 4 * (size_t)plan.row_off[r], n,
                          plan.n[r], plan.surf[r], groups, run, part, skip);
@@ -291,6 +345,29 @@ hipError_t launch_skin_moments(int precision, const void* d_pts, const int32_t* 
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t launch_skin_moments(int precision, const void* d_pts, const int32_t* d_kstar, const void* d_rows, int64_t n,
+                               const SkinPlan& plan, double* d_partials, double* d_moments, hipStream_t s,
+                               const int* skip) {
+  return launch_skin_moments_impl(precision, d_pts, d_kstar, d_rows, n, plan, d_partials, d_moments, s, skip, nullptr);
+}
+
+// Σ aw j jᵀ: the factor of resident point i from d_d[i] (the pass's d* in resident order), the
+// loss, d_conf (null: no weights), d_perm and n_surface (< 0: no split), as launch_robust's
+hipError_t launch_skin_moments_weighted(int precision, const void* d_pts, const int32_t* d_kstar, const double* d_d,
+                                        const void* d_rows, const double* d_conf, const int32_t* d_perm,
+                                        int64_t n_surface, int kind, double scale, int64_t n, const SkinPlan& plan,
+                                        double* d_partials, double* d_moments, hipStream_t s) {
+  if (!d_d || !robust::valid(kind, scale)) return hipErrorInvalidValue;
+  SkinFactor fac;
+  fac.dstar = d_d;
+  fac.conf = d_conf;
+  fac.perm = d_perm;
+  fac.n_surface = n_surface;
+  fac.kind = kind;
+  fac.scale = scale;
+  return launch_skin_moments_impl(precision, d_pts, d_kstar, d_rows, n, plan, d_partials, d_moments, s, nullptr, &fac);
 }
 
 }  // namespace fsdf

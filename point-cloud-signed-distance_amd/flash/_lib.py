@@ -139,6 +139,10 @@ _PROTOS = {
     "fsdf_get_free_split": (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int32)]),
     "fsdf_set_free_space": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
     "fsdf_get_free_space": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), c_void_p]),
+    "fsdf_set_robust_skins": (c_int32, [c_void_p, c_int32]),
+    "fsdf_get_robust_skins": (c_int32, [c_void_p, POINTER(c_int32)]),
+    "fsdf_eval_robust_skins": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -681,6 +685,44 @@ class Context:
               self._ctx, "eval_skin_moments")
         off = np.concatenate([[0], np.cumsum([m * m for m in ms])]).astype(int)
         return cost.value, accum, [flat[off[i]: off[i + 1]].reshape(m, m) for i, m in enumerate(ms)]
+
+    def set_robust_skins(self, enable: bool):
+        """fsdf_set_robust_skins: the robust objective (a loss, point weights,
+        a free split) also serves scenes with RBF skins and deformations —
+        value_and_gradient and descend's host loop, and with set_lm_skins(True)
+        value_gradient_hessian and descend_lm's. Off by default: such scenes
+        are then refused as before. A context setting."""
+        check(self._lib.fsdf_set_robust_skins(self._ctx, int(bool(enable))), self._ctx, "set_robust_skins")
+        self.robust_skins = bool(enable)
+
+    def get_robust_skins(self) -> bool:
+        """fsdf_get_robust_skins: the switch as the library holds it."""
+        v = c_int32(0)
+        check(self._lib.fsdf_get_robust_skins(self._ctx, ctypes.byref(v)), self._ctx, "get_robust_skins")
+        return bool(v.value)
+
+    def eval_robust_skins(self, poses, moments: bool = True):
+        """fsdf_eval_robust_skins (needs set_robust_skins(True)): one pass over
+        the resident cloud at the current rows (set_rbf_params) and the sums of
+        the context's robust objective -> (cost = Σρ, accum in eval's full
+        layout: a hull's robust wrench, a skin's wrench 0, then the skins'
+        blocks Σ 2 (aw d*) j; moments [K, 21] with a skin's row zero, or None;
+        [Σ aw j jᵀ [4n+4, 4n+4] per skin, in surface order], or None;
+        weights [K] = Σ aw)."""
+        p = self._poses(poses)
+        accum = np.empty(self.accum_len, np.float64)
+        mom = np.empty((self.K, 21), np.float64) if moments else None
+        ms = [4 * n + 4 for n in self.rbf_centres]
+        flat = np.empty(sum(m * m for m in ms), np.float64) if moments else None
+        wts = np.empty(self.K, np.float64)
+        cost = c_double(0.0)
+        check(self._lib.fsdf_eval_robust_skins(self._ctx, ptr(p), ctypes.byref(cost), ptr(accum), ptr(mom), ptr(flat),
+                                               ptr(wts)), self._ctx, "eval_robust_skins")
+        skin_mom = None
+        if moments:
+            off = np.concatenate([[0], np.cumsum([m * m for m in ms])]).astype(int)
+            skin_mom = [flat[off[i]: off[i + 1]].reshape(m, m) for i, m in enumerate(ms)]
+        return cost.value, accum, mom, skin_mom, wts
 
     def eval_device(self, poses, d_accum: int, d_kstar: int = 0, d_d: int = 0, d_grad: int = 0):
         """Asynchronous pass writing into device buffers (raw device pointers)."""

@@ -122,7 +122,8 @@ class CostFunctor:
     only where the model covers it (include/flashsdf.h "free space")."""
 
     def __init__(self, manipulator: Manipulator, sensed_points, device: int = 0, precision: int = 64,
-                 deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False, loss=None):
+                 deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False, loss=None,
+                 robust_skins: bool = False):
         self.manipulator = manipulator
         self.weight = deformation_cost_weight
         self.state = ManipulatorState(manipulator)
@@ -147,9 +148,16 @@ class CostFunctor:
         self.skin_hessian = False
         if skin_hessian:
             self.set_skin_hessian(True)
+        # robust_skins: a loss, point weights and a free split also serve native
+        # scenes with RBF skins and deformations (fsdf_set_robust_skins; the
+        # skins' robust blocks are reduced on the device, csrc/robust_skin.hip)
+        self.robust_skins = False
+        if robust_skins:
+            self.set_robust_skins(True)
         # loss: a robust point loss (flash.robust.Huber / Tukey; None: least
         # squares) for __call__, value_and_gradient, value_gradient_hessian,
-        # descend and descend_lm (fsdf_set_loss; native rigid scenes)
+        # descend and descend_lm (fsdf_set_loss; native rigid scenes, others
+        # with robust_skins)
         self.loss = None
         self.set_loss(loss)
         # point_weights: one confidence weight per sensed point (set_point_weights;
@@ -212,11 +220,11 @@ class CostFunctor:
         one per sensed point in the order of `sensed_points` (None: none):
         Σ a ρ(d*) in place of Σ ρ(d*), its gradient and the Gauss-Newton Hessian
         (fsdf_set_point_weights; the robust reduction, also without a loss).
-        Native rigid scenes only. They belong to the sensed cloud:
+        Native rigid scenes, others with robust_skins. They belong to the sensed cloud:
         set_sensed_points drops them. per_point and the least-squares queries
         of the context are not affected."""
         if weights is not None:
-            if not (self._native and self.rigid):
+            if not self._robust_capable():
                 raise NotImplementedError(
                     "point weights: they serve native rigid scenes (no RBF skin, no deformation)")
             weights = np.array(weights, np.float64, copy=True).reshape(-1)
@@ -232,12 +240,12 @@ class CostFunctor:
         to be empty and count only where the model covers them (d* < 0) —
         Σ_surface ρ(d*) + Σ_free [d* < 0] ρ(d*), its gradient and Gauss-Newton
         Hessian (fsdf_set_free_split; the robust reduction, also without a
-        loss). None or n clears it. Native rigid scenes only. It belongs to
+        loss). None or n clears it. Native rigid scenes, others with robust_skins. It belongs to
         the sensed cloud: set_sensed_points drops it (a DepthFrame with
         free_space sets its own)."""
         n = self.n_points if n_surface is None else int(n_surface)
         if n != self.n_points:
-            if not (self._native and self.rigid):
+            if not self._robust_capable():
                 raise NotImplementedError("free split: it serves native rigid scenes (no RBF skin, no deformation)")
             if not 0 <= n <= self.n_points:
                 raise ValueError(f"free split: n_surface {n} of {self.n_points} sensed points")
@@ -249,17 +257,36 @@ class CostFunctor:
         """The robust point loss of this functor's objective (flash.robust;
         None: least squares, the default): Σρ(d*) in place of Σd*², its
         gradient, and the IRLS Gauss-Newton Hessian (fsdf_set_loss; reduced on
-        the device, csrc/robust.hip). Native rigid scenes only. per_point and
+        the device, csrc/robust.hip). Native rigid scenes, others with
+        robust_skins (csrc/robust_skin.hip). per_point and
         the least-squares queries of the context are not affected."""
-        if loss is not None and not (self._native and self.rigid):
+        if loss is not None and not self._robust_capable():
             raise NotImplementedError("loss: robust losses serve native rigid scenes (no RBF skin, no deformation)")
         self.loss = loss
         self._assert_loss()
+
+    def _robust_capable(self):
+        # a robust objective: native rigid scenes, and with robust_skins any native scene
+        return self._native and (self.rigid or self.robust_skins)
+
+    def set_robust_skins(self, enable: bool = True):
+        """Let the robust objective (set_loss, set_point_weights,
+        set_free_split, a DepthFrame's free_space) serve scenes with RBF skins
+        and deformations (fsdf_set_robust_skins); native scenes only.
+        value_gradient_hessian / descend_lm on such a scene need skin_hessian
+        as well."""
+        if enable and not self._native:
+            raise NotImplementedError("robust_skins: scene is not native-capable")
+        self.robust_skins = bool(enable)
+        if self._native:
+            self.ctx.set_robust_skins(self.robust_skins)
 
     def _assert_loss(self):
         # (the engine is shared: another functor of it may have set its own)
         if self.ctx.loss != self.loss:
             self.ctx.set_loss(self.loss)
+        if self._native and getattr(self.ctx, "robust_skins", False) != self.robust_skins:
+            self.ctx.set_robust_skins(self.robust_skins)
 
     def set_skin_hessian(self, enable: bool = True):
         """Turn the Gauss-Newton Hessian of non-rigid scenes on or off

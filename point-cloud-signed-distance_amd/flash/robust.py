@@ -103,6 +103,29 @@ def parse(spec):
     return kinds[name](float(scale))
 
 
+def _point_factors(dd, loss, weights, one_sided, who):
+    """(aw, a·ρ) per point in the dtype of dd, formed as csrc/robust.hip forms
+    them: w = w(d) and ρ of `loss` (None: 1, d²), a = weights (None: 1) through
+    the one-sided gate (one_sided: True for a free-space sample, which keeps
+    its a only where d < 0 and gets exactly 0 elsewhere), one product aw."""
+    t = dd.dtype.type
+    w = np.ones_like(dd) if loss is None else loss.weight(dd)
+    rho = dd * dd if loss is None else loss.rho(dd)
+    a = None
+    if weights is not None:
+        a = np.asarray(weights, dd.dtype)
+        if a.shape != dd.shape:
+            raise ValueError(f"{who}: {a.shape} weights for {dd.shape} points")
+    if one_sided is not None:
+        free = np.asarray(one_sided)
+        if free.dtype != np.bool_ or free.shape != dd.shape:
+            raise ValueError(f"{who}: one_sided is a boolean mask per point, got {free.dtype} {free.shape}")
+        a = np.where(~free | (dd < 0), np.ones_like(dd) if a is None else a, t(0))
+    if a is not None:
+        w, rho = a * w, a * rho
+    return w, rho
+
+
 def weighted_sums(points, kstar, d, grad, n_surfaces, loss=None, weights=None, one_sided=None):
     """The per-surface sums of the (weighted) robust objective in plain numpy,
     from per-point outputs (include/flashsdf.h "per-point confidence
@@ -123,20 +146,7 @@ def weighted_sums(points, kstar, d, grad, n_surfaces, loss=None, weights=None, o
     t = dd.dtype.type
     P, G = np.asarray(points, dd.dtype), np.asarray(grad, dd.dtype)
     k = np.asarray(kstar)
-    w = np.ones_like(dd) if loss is None else loss.weight(dd)
-    rho = dd * dd if loss is None else loss.rho(dd)
-    a = None
-    if weights is not None:
-        a = np.asarray(weights, dd.dtype)
-        if a.shape != dd.shape:
-            raise ValueError(f"weighted_sums: {a.shape} weights for {dd.shape} points")
-    if one_sided is not None:
-        free = np.asarray(one_sided)
-        if free.dtype != np.bool_ or free.shape != dd.shape:
-            raise ValueError(f"weighted_sums: one_sided is a boolean mask per point, got {free.dtype} {free.shape}")
-        a = np.where(~free | (dd < 0), np.ones_like(dd) if a is None else a, t(0))
-    if a is not None:
-        w, rho = a * w, a * rho
+    w, rho = _point_factors(dd, loss, weights, one_sided, "weighted_sums")
     v = np.concatenate([G, np.cross(P, G)], axis=1)
     term = v * (t(2) * (w * dd))[:, None]
     iu = np.triu_indices(6)
@@ -150,3 +160,59 @@ def weighted_sums(points, kstar, d, grad, n_surfaces, loss=None, weights=None, o
         cost[s], wrench[s], W[s] = rho[sel].sum(), term[sel].sum(0), w[sel].sum()
         moments[s] = np.einsum("ni,nj->ij", v[sel] * w[sel, None], v[sel])[iu]
     return cost, wrench, moments, W
+
+
+def _skins(solves_or_rows):
+    """[(surface, centres [n, 3], u [n + 4])]: of flash.rbf.solve's RbfSolves
+    (their .surface, .centres, .u), or of (surface, rows [n + 1, 4]) pairs —
+    a skin's rows as set_rbf_params takes them (centre and weight per centre,
+    then (a, b))."""
+    out = []
+    for r in solves_or_rows:
+        if hasattr(r, "centres"):
+            out.append((int(r.surface), np.asarray(r.centres), np.asarray(r.u)))
+        else:
+            surface, rows = r
+            rows = np.asarray(rows)
+            out.append((int(surface), rows[:-1, :3], np.concatenate([rows[:-1, 3], rows[-1]])))
+    return out
+
+
+def weighted_skin_blocks(points, kstar, d, solves_or_rows, loss=None, weights=None, one_sided=None,
+                         dtype=np.float64):
+    """The RBF skins' blocks of the accumulator under the (weighted) robust
+    objective in plain numpy (include/flashsdf.h "robust objectives on skins"):
+    per skin Σ 2 (aw d) j over the points with k* = the skin's surface, j the
+    point's row of flash.rbf.skin_jacobian (the block's layout) and aw as
+    weighted_sums forms it. With no loss, weights or mask: Σ 2 d j, the pass's
+    own block. Returns one [4n + 4] array per skin, in the order given.
+    dtype: the arithmetic's (np.longdouble measures float64's own rounding)."""
+    from . import rbf
+    dd = np.asarray(d, dtype)
+    P, k = np.asarray(points, dtype).reshape(-1, 3), np.asarray(kstar)
+    aw, _ = _point_factors(dd, loss, weights, one_sided, "weighted_skin_blocks")
+    t = dd.dtype.type(2) * (aw * dd)
+    out = []
+    for surface, C, u in _skins(solves_or_rows):
+        sel = k == surface
+        J = rbf.skin_jacobian(C, u, P[sel], dtype=dtype)
+        out.append((J * t[sel, None]).sum(0))
+    return out
+
+
+def weighted_skin_moments(points, kstar, d, solves_or_rows, loss=None, weights=None, one_sided=None,
+                          dtype=np.float64):
+    """The skins' weighted second moments Σ aw j jᵀ — the Gauss-Newton (IRLS)
+    term of the robust objective on a skin, as weighted_skin_blocks: one
+    [4n + 4, 4n + 4] array per skin. With no loss, weights or mask: Σ j jᵀ
+    (csrc/skin_moments.hip)."""
+    from . import rbf
+    dd = np.asarray(d, dtype)
+    P, k = np.asarray(points, dtype).reshape(-1, 3), np.asarray(kstar)
+    aw, _ = _point_factors(dd, loss, weights, one_sided, "weighted_skin_moments")
+    out = []
+    for surface, C, u in _skins(solves_or_rows):
+        sel = k == surface
+        J = rbf.skin_jacobian(C, u, P[sel], dtype=dtype)
+        out.append((J * aw[sel, None]).T @ J)
+    return out

@@ -206,7 +206,8 @@ def _frame_weights(weights, points):
     return np.asarray(weights, np.float64).reshape(-1)
 
 
-def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, loss=None, weights=None):
+def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, loss=None, weights=None,
+              robust_skins: bool = False):
     """wrapped_cost (src/tracking.jl:16-21) over a CostFunctor, then optimize!.
     Without a callback, a NaiveSolver runs natively (fsdf_descend: the same
     arithmetic, no Python round trip per iteration), and so does a
@@ -223,8 +224,14 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, l
     weights (one confidence weight per point of the functor's cloud; None: the
     functor as it is): handed to the functor (CostFunctor.set_point_weights)
     before anything runs, under the loss's rules. n_points stays the divisor:
-    pass weights of mean 1 for c / Σa."""
+    pass weights of mean 1 for c / Σa.
+    robust_skins (False: the functor as it is): turned on in the functor
+    (CostFunctor.set_robust_skins) before the loss and the weights are handed
+    over, so a native scene with RBF skins or deformations accepts them; a
+    LevenbergMarquardt on such a scene needs skins=True as well."""
     n = max(n_points, 1)
+    if robust_skins:
+        cost.set_robust_skins(True)
     if loss is not None:
         cost.set_loss(loss)
     if weights is not None:
@@ -276,7 +283,7 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, l
 
 
 def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callback=None, solver=None,
-                   device: int = 0, precision: int = 64, loss=None, weights=None):
+                   device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False):
     """Tracking.estimate_state (src/tracking.jl:8-27). Returns the solution x.
 
     The default callback accepts (x, c): the reference's default `x -> ()` is
@@ -287,6 +294,8 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
     callable points -> weights, e.g. depthsensors.depth_noise_weights bound to
     a sensor pose): the objective is Σ a ρ(d*) / N — native rigid scenes; set
     after the cloud is resident.
+    robust_skins: loss, weights and a frame's free space also serve native
+    scenes with RBF skins and deformations (fsdf_set_robust_skins).
     sensed_points may be a depthsensors.DepthFrame (the depth image, the
     sensor and its pose): the device forms the cloud (fsdf_set_depth_*), N is
     the number of valid pixels, and the host forms the points only for a
@@ -298,13 +307,14 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
     pixel)."""
     solver = solver or _default_solver(manipulator)
     if isinstance(sensed_points, DepthFrame):
-        cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision)
+        cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision,
+                           robust_skins=robust_skins)
         pts = lambda: cost.sensed_points  # noqa: E731 (formed when asked for)
     else:
         pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
-        cost = CostFunctor(manipulator, pts, device=device, precision=precision)
+        cost = CostFunctor(manipulator, pts, device=device, precision=precision, robust_skins=robust_skins)
     return _optimize(cost, cost.n_points, x_estimated, callback, solver, loss=loss,
-                     weights=_frame_weights(weights, pts))
+                     weights=_frame_weights(weights, pts), robust_skins=robust_skins)
 
 
 def notebook_frame_solver(manipulator):
@@ -320,11 +330,13 @@ class Tracker:
     iteration are recorded (host FK + pass + chain rule, end to end)."""
 
     def __init__(self, manipulator: Manipulator, state: ManipulatorState | None = None, solver=None,
-                 device: int = 0, precision: int = 64, loss=None, weights=None):
+                 device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False):
         self.manipulator = manipulator
         self.state = state if state is not None else ManipulatorState(manipulator)
         self.solver = solver or notebook_frame_solver(manipulator)
-        self.cost = CostFunctor(manipulator, np.zeros((0, 3)), device=device, precision=precision)
+        self.cost = CostFunctor(manipulator, np.zeros((0, 3)), device=device, precision=precision,
+                                robust_skins=robust_skins)
+        self.robust_skins = bool(robust_skins)  # loss / weights / free space also on skins and deformations
         self.loss = loss  # a robust point loss for every frame (flash.robust; None: least squares)
         # per-point confidence weights: a callable points -> weights applied to every frame (an
         # array fits one frame only: give it to step); None: every point counts 1
@@ -356,7 +368,7 @@ class Tracker:
         t1 = time.perf_counter()
         w = _frame_weights(self.weights if weights is None else weights, pts)
         x = _optimize(self.cost, self.cost.n_points, flatten(self.state), callback, self.solver, loss=self.loss,
-                      weights=w)
+                      weights=w, robust_skins=self.robust_skins)
         unflatten(self.state, x)
         t2 = time.perf_counter()
         self.set_points_ms.append((t1 - t0) * 1e3)
@@ -371,7 +383,7 @@ class Tracker:
 
 
 def track(manipulator: Manipulator, frames, state: ManipulatorState | None = None, solver=None, callback=None,
-          device: int = 0, precision: int = 64, loss=None, weights=None):
+          device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False):
     """for event in log: gradient_descent!(state, model, sensed_points)
     (examples/irb_and_squishable.ipynb cells 11-12). `frames` yields sensed
     clouds ([n,3]) or depthsensors.DepthFrames (made resident by the device
@@ -380,8 +392,10 @@ def track(manipulator: Manipulator, frames, state: ManipulatorState | None = Non
     per-frame solutions [F, n_states], the Tracker).
     loss: a robust point loss for every frame (flash.robust).
     weights: a callable points -> weights applied to every frame (or one array,
-    where every frame has as many points)."""
-    tr = Tracker(manipulator, state, solver, device, precision, loss=loss, weights=weights)
+    where every frame has as many points).
+    robust_skins: as estimate_state's."""
+    tr = Tracker(manipulator, state, solver, device, precision, loss=loss, weights=weights,
+                 robust_skins=robust_skins)
     xs = []
     it = iter(frames)
     cur = next(it, None)
