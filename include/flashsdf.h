@@ -604,7 +604,8 @@ int fsdf_get_point_weights(fsdf_ctx* ctx, double* out /* [n], resident order, or
  *
  * Not done: a prefetched depth frame (fsdf_prefetch_points has no depth form: a
  * live sensor has no next frame); ranged and keyed (sharded) depth frames;
- * weights computed on the device (the caller forms them from the pixel list).
+ * weights computed on the device other than a voxel grid's multiplicities
+ * ("voxel grid" below; the caller forms any others from the pixel list).
  * The free-space term for what the rays passed through and for the pixels that
  * saw nothing: "free space" below. */
 enum { FSDF_DEPTH_RANGE = 0, FSDF_DEPTH_Z = 1 };
@@ -705,6 +706,98 @@ int fsdf_get_free_split(const fsdf_ctx* ctx, int64_t* n_surface_out, int32_t* se
 int fsdf_set_free_space(fsdf_ctx* ctx, int32_t samples /* J, 0..16; 0 = off */, int32_t stride /* >= 1 */,
                         const double* lengths /* [3]: gap >= 0, spacing > 0, miss_range >= 0 */);
 int fsdf_get_free_space(const fsdf_ctx* ctx, int32_t* samples_out, int32_t* stride_out, double* lengths_out /* [3] */);
+
+/* ---- voxel grid ------------------------------------------------------------------
+ * A depth frame is hundreds of thousands of points, 2-4 mm apart at 1-2 m
+ * range: far denser than the scale the model's geometry varies on, and a
+ * frame's cost is its point count times the solver's iterations. A voxel grid
+ * thins the cloud before the solver sees it: one centroid per occupied cell,
+ * and the cell's population as that point's weight, so that Σ a ρ(d*) over the
+ * centroids approximates the full frame's objective at an even spatial density.
+ * The stage runs on the device (csrc/voxel.hip) ahead of the path of
+ * fsdf_set_points_device; the pass and the solver kernels are not involved.
+ *
+ * The definition (flash/depthdata.py voxel_downsample restates it operation for
+ * operation: the same bits). The grid has a cell size h (finite, > 0) and an
+ * origin o (3 finite doubles); it is anchored in the world, so cells do not
+ * move from frame to frame. All arithmetic is fp64 in every context precision
+ * and uncontracted. Per point and axis:
+ *   q = floor((x − o) / h)          (the division correctly rounded)
+ *   c = q clamped to [−2^20, 2^20 − 1], as int32
+ *   key = (c_z + 2^20) << 42 | (c_y + 2^20) << 21 | (c_x + 2^20)      (63 bits)
+ * A point with a non-finite coordinate belongs to no voxel: it is dropped and
+ * counted (its key is all ones). Voxels are ordered by ascending key — the
+ * CALLER ORDER of the downsampled cloud — and within a voxel the points stay in
+ * ascending input index (a stable sort). A voxel's centroid is, per coordinate,
+ * the left fold in that order, acc = p_first; acc = acc + p_next; ..., then
+ * acc / (double)count: no floating-point atomics and no tree whose shape
+ * depends on the launch geometry, so the result is a function of the input
+ * array alone, the same from run to run. The fold runs on one lane per voxel
+ * and is linear in the largest cell's population (a few to a few dozen points
+ * on camera data).
+ *
+ * fsdf_set_voxel_grid: a context setting like the sensor and the free-space
+ * setting, kept over frames and model swaps. size 0 turns it off (origin and
+ * weights are then ignored); origin NULL is (0, 0, 0); weights FSDF_VOXEL_COUNT
+ * or FSDF_VOXEL_UNIT. A size that is negative or not finite, an origin entry
+ * that is not finite or an unknown mode is FSDF_ERR_ARG and the earlier setting
+ * stays. fsdf_set_voxel_grid_ref is the same with the size read through a
+ * pointer (NULL reads as 0), for bindings that pass every floating-point
+ * argument by reference (julia/FlashSDF.jl). fsdf_get_voxel_grid reads the
+ * setting back; any output may be NULL.
+ *
+ * fsdf_set_points_voxel / _device: xyz [n][3] fp64 (host / device) is
+ * downsampled, and the centroids [m][3] then take exactly the path of
+ * fsdf_set_points_device. Under FSDF_VOXEL_COUNT the point weights are then set
+ * to (double)count through the path of fsdf_set_point_weights_device (so the
+ * robust reduction serves the objective, also under FSDF_LOSS_SQUARE); under
+ * FSDF_VOXEL_UNIT no weights are set. With no grid set: FSDF_ERR_STATE.
+ * n >= 2^31: FSDF_ERR_ARG. n == 0, or every point dropped, makes a cloud of 0
+ * points resident: not an error. Synchronous like fsdf_set_points. It costs one
+ * sizing synchronisation, for m and the number dropped. fsdf_set_points,
+ * _device, _prefetched, _range* and _keyed_device ignore the grid, and each
+ * ends a voxel cloud's lists as it ends a depth frame's pixel list.
+ *
+ * Depth frames. With a grid set, every fsdf_set_depth_* downsamples its
+ * observed points (the valid pixels' points, in pixel order) between the
+ * scatter and the path of fsdf_set_points_device: one more sizing
+ * synchronisation per frame. With free-space samples configured the samples
+ * follow the centroids unchanged, the split is set to m, and under
+ * FSDF_VOXEL_COUNT the weights are the counts followed by 1.0 per sample.
+ * fsdf_get_depth_pixels returns, for a voxel, the pixel of its first point (the
+ * lowest pixel index in the cell) and the samples' pixels as before. With
+ * size 0 a frame runs the launches it ran before and returns the bits it
+ * returned before.
+ *
+ * fsdf_get_voxels: of the resident voxel cloud, xyz_out [m][3] the centroids,
+ * count_out [m], cell_out [m][3] the cells (c_x, c_y, c_z), all in caller
+ * order; *m_out, *n_in_out the number of input points (a depth frame: of valid
+ * pixels), *dropped_out of dropped ones. Any pointer may be NULL (read m first).
+ * fsdf_get_voxel_of_point: out[i] = the caller index of input point i's voxel,
+ * −1 for a dropped point; out may be NULL to read n_in alone. Both return
+ * FSDF_ERR_STATE when the resident cloud did not come through the grid.
+ * Synchronous.
+ *
+ * A later fsdf_set_point_weights replaces the counts, as with any weights; the
+ * caller who wants both multiplies by count_out. The solver loops' n_points
+ * divisor is the caller's as before.
+ *
+ * Not done: prefetched, ranged, keyed and sharded voxel clouds; centroids
+ * weighted by caller weights (weights are set after the cloud); voxelised
+ * free-space samples (their stride thins them); a parallel fold for a cell
+ * with very many points (the one-lane fold's worst case is the whole cloud in
+ * one cell). */
+enum { FSDF_VOXEL_UNIT = 0, FSDF_VOXEL_COUNT = 1 };
+int fsdf_set_voxel_grid(fsdf_ctx* ctx, double size /* 0 = off */, const double* origin /* [3] or NULL */,
+                        int32_t weights);
+int fsdf_set_voxel_grid_ref(fsdf_ctx* ctx, const double* size, const double* origin /* [3] or NULL */,
+                            int32_t weights);
+int fsdf_get_voxel_grid(const fsdf_ctx* ctx, double* size_out, double* origin_out /* [3] */, int32_t* weights_out);
+int fsdf_set_points_voxel(fsdf_ctx* ctx, const double* xyz, int64_t n);
+int fsdf_set_points_voxel_device(fsdf_ctx* ctx, const double* d_xyz, int64_t n);
+int fsdf_get_voxels(fsdf_ctx* ctx, double* xyz_out /* [m][3] */, int32_t* count_out /* [m] */,
+                    int32_t* cell_out /* [m][3] */, int64_t* m_out, int64_t* n_in_out, int64_t* dropped_out);
+int fsdf_get_voxel_of_point(fsdf_ctx* ctx, int32_t* out /* [n_in] or NULL */, int64_t* n_in_out);
 
 /* ---- Gauss-Newton for RBF skins: device side -----------------------------------
  * The skins' second moments M_r above, reduced on the device

@@ -228,6 +228,51 @@ function free_split(ctx::Context)
     set[] == 0 ? nothing : Int(n[])
 end
 
+"""
+The voxel grid that set_points_voxel! and every later set_depth! thin their cloud through
+(fsdf_set_voxel_grid, with the size by reference): one centroid per occupied cell of side `size`
+counted from `origin`, in ascending cell order; `count_weights = true`: the cells' populations become
+the point weights. `size = 0` turns it off. Kept over frames and model swaps.
+"""
+set_voxel_grid!(ctx::Context, size::Real; origin::AbstractVector=[0.0, 0.0, 0.0], count_weights::Bool=true) =
+    check(ctx.ptr, ccall((:fsdf_set_voxel_grid_ref, lib), Cint, (Ptr{Void}, Ptr{Float64}, Ptr{Float64}, Int32),
+                         ctx.ptr, Float64[size], convert(Vector{Float64}, origin), Int32(count_weights ? 1 : 0)),
+          "set_voxel_grid")
+
+"set_points! through the context's voxel grid: the cells' centroids become the resident cloud (fsdf_set_points_voxel)."
+function set_points_voxel!{T}(ctx::Context, points::AbstractVector{SVector{3, T}})
+    P = convert(Vector{SVector{3, Float64}}, points)
+    check(ctx.ptr, ccall((:fsdf_set_points_voxel, lib), Cint, (Ptr{Void}, Ptr{Float64}, Int64),
+                         ctx.ptr, reinterpret(Float64, P), length(P)), "set_points_voxel")
+end
+
+"""
+Of the resident voxel cloud: (centroids, counts, cells [3, m], number of input points, number dropped as
+non-finite), the voxels in the cloud's order (fsdf_get_voxels).
+"""
+function voxels(ctx::Context)
+    m, n_in, dropped = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ctx.ptr, ccall((:fsdf_get_voxels, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                         ctx.ptr, C_NULL, C_NULL, C_NULL, m, n_in, dropped), "get_voxels")
+    xyz, count, cell = zeros(Float64, 3, m[]), zeros(Int32, m[]), zeros(Int32, 3, m[])
+    check(ctx.ptr, ccall((:fsdf_get_voxels, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                         ctx.ptr, xyz, count, cell, m, n_in, dropped), "get_voxels")
+    ([SVector{3, Float64}(xyz[:, i]) for i in 1:m[]], count, cell, Int(n_in[]), Int(dropped[]))
+end
+
+"For every input point the 1-based index of its voxel in the resident cloud, 0 for a dropped point (fsdf_get_voxel_of_point)."
+function voxel_of_point(ctx::Context)
+    n = Ref{Int64}(0)
+    check(ctx.ptr, ccall((:fsdf_get_voxel_of_point, lib), Cint, (Ptr{Void}, Ptr{Int32}, Ref{Int64}),
+                         ctx.ptr, C_NULL, n), "get_voxel_of_point")
+    out = zeros(Int32, n[])
+    check(ctx.ptr, ccall((:fsdf_get_voxel_of_point, lib), Cint, (Ptr{Void}, Ptr{Int32}, Ref{Int64}),
+                         ctx.ptr, out, n), "get_voxel_of_point")
+    out .+ Int32(1)
+end
+
 "One GPU's shard of the frame's cloud (the cost is a sum over points,
 src/gradientdescent.jl:32): the whole cloud is Hilbert-sorted on the device and
 this context keeps the contiguous range [first, last] (1-based, inclusive) of

@@ -92,6 +92,7 @@ static int set_points_impl(fsdf_ctx* c, const double* src, int64_t n, bool devic
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
   c->free_split = -1;                    // (and so does the split of its free-space samples)
   c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
+  c->voxel_cloud = false;                // (and a voxel cloud's lists)
   const double* d_src = src;
   if (!device_src && n > 0) {
     HIPCHECK(c, c->staging.reserve((size_t)n * 3));
@@ -250,6 +251,7 @@ extern "C" int fsdf_set_points_keyed_device(fsdf_ctx* c, const double* d_xyz, co
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
   c->free_split = -1;                    // (and so does the split of its free-space samples)
   c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
+  c->voxel_cloud = false;                // (and a voxel cloud's lists)
   HIPCHECK(c, c->cur.pts.reserve((size_t)std::max<int64_t>(n, 1) * 3 * point_bytes(c)));
   HIPCHECK(c, c->cur.perm.reserve((size_t)std::max<int64_t>(n, 1)));
   if (n > 0) {
@@ -328,6 +330,34 @@ extern "C" int fsdf_get_sensor(const fsdf_ctx* c, int32_t* rows_out, int32_t* co
   return FSDF_OK;
 }
 
+// A frame under a voxel grid (fsdf_set_voxel_grid; voxel.hip): `staging` holds
+// the frame's n_surface observed points, then `tail` free-space samples, and
+// depth_pix their pixels. The observed points become their m voxel centroids —
+// one more sizing synchronisation, for m —, the samples follow unchanged
+// (c->voxel.cloud), a voxel's pixel is its first point's, the split is m, and
+// under FSDF_VOXEL_COUNT the weights are the counts, then 1.0 per sample.
+static int set_depth_voxel(fsdf_ctx* c, int64_t n_surface, int64_t tail, const char* who) {
+  int rc = voxel_downsample(c, c->staging.get(), n_surface, who);
+  if (rc) return rc;
+  rc = voxel_finish(c, tail, c->depth_pix.get());
+  if (rc) return rc;
+  const int64_t m = c->vox_m, n = m + tail;
+  HIPCHECK(c, c->voxel.cloud.reserve((size_t)std::max<int64_t>(n, 1) * 3));
+  if (m > 0)
+    HIPCHECK(c, hipMemcpyAsync(c->voxel.cloud.get(), c->voxel.xyz.get(), (size_t)m * 3 * sizeof(double),
+                               hipMemcpyDeviceToDevice, c->stream));
+  if (tail > 0)
+    HIPCHECK(c, hipMemcpyAsync(c->voxel.cloud.get() + 3 * m, c->staging.get() + 3 * n_surface,
+                               (size_t)tail * 3 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  c->depth_pix.swap(c->voxel.pix);  // (stream-ordered: the finish kernel read the old list)
+  rc = set_points_impl(c, c->voxel.cloud.get(), n, true, 0, n);
+  if (rc) return rc;
+  c->depth_cloud = true;
+  c->voxel_cloud = true;
+  c->free_split = m < n ? m : -1;
+  return voxel_set_weights(c);
+}
+
 // A frame: count and scan, the 8-byte total back (the one synchronisation that
 // sizes the cloud), the scatter into `staging`, and from there the frame is
 // fsdf_set_points_device of that array.
@@ -402,6 +432,7 @@ static int set_depth_impl(fsdf_ctx* c, const void* depth, int format, bool devic
                                    c->depth_counts.get(), c->staging.get(), c->depth_pix.get(), c->stream);
     if (e != hipSuccess) return fail(c, FSDF_ERR_HIP, "%s (scatter): %s", who, hipGetErrorString(e));
   }
+  if (c->vox_size > 0.0) return set_depth_voxel(c, n_surface, n - n_surface, who);
   const int rc = set_points_impl(c, c->staging.get(), n, true, 0, n);
   if (rc) return rc;
   c->depth_cloud = true;
@@ -575,6 +606,7 @@ extern "C" int fsdf_set_points_prefetched(fsdf_ctx* c) {
   c->conf_set = c->conf_stale = false;  // (weights belong to the cloud that leaves)
   c->free_split = -1;                    // (and so does the split of its free-space samples)
   c->depth_cloud = false;                // (and so do a depth frame's pixel indices)
+  c->voxel_cloud = false;                // (and a voxel cloud's lists)
   std::swap(c->cur, c->next);
   return finish_resident(c, n, false, true);
 }

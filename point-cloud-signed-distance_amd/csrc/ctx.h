@@ -1,6 +1,7 @@
 // ctx.h — the context behind include/flashsdf.h, shared by the host-side
 // translation units: capi.hip (context, model, queries), cloud.hip (resident
-// cloud), point_weights.hip (its per-point confidence weights), pass.hip (the
+// cloud), point_weights.hip (its per-point confidence weights), voxel.hip (its
+// voxel-grid downsampling), pass.hip (the
 // residual pass), iterate.hip (mechanism, one iteration), descend.hip (the
 // solver loops).
 //
@@ -58,6 +59,25 @@ struct ResidentCloud {
   fsdf::DevBuf<unsigned char> pts;
   fsdf::DevBuf<int32_t> perm;
   fsdf::DevBuf<float> chunk_ws;
+};
+
+// the voxel-grid stage (voxel.hip): the (key, index) pairs double-buffered — the
+// sorted pairs are k0 / i0 —, rocPRIM's temporary storage, the head-flag counts
+// [2][blocks] and totals {m, dropped} with their pinned read-back, each voxel's
+// first sorted position; then the lists kept for fsdf_get_voxels /
+// fsdf_get_voxel_of_point, the weights and a depth frame's pixel list and cloud
+struct VoxelBuffers {
+  fsdf::DevBuf<uint64_t> k0, k1;
+  fsdf::DevBuf<int32_t> i0, i1, counts, start;
+  fsdf::DevBuf<unsigned char> tmp;
+  fsdf::DevBuf<int64_t> total;
+  fsdf::PinnedBuf<int64_t> h_total;
+  fsdf::DevBuf<double> xyz;                     // [m][3] centroids
+  fsdf::DevBuf<int32_t> count, cell, first;     // [m], [m][3], [m]
+  fsdf::DevBuf<int32_t> of_point;               // [n_in]
+  fsdf::DevBuf<double> weights;                 // [m + tail] (double)count, then 1.0 per free-space sample
+  fsdf::DevBuf<int32_t> pix;                    // [m + tail] a depth frame's pixel list (swapped into depth_pix)
+  fsdf::DevBuf<double> cloud;                   // [m + tail][3] a depth frame's centroids, then its samples
 };
 
 struct fsdf_ctx {
@@ -214,6 +234,15 @@ struct fsdf_ctx {
   int64_t free_split = -1;
   int free_samples = 0, free_stride = 1;
   double free_gap = 0.0, free_spacing = 0.0, free_miss = 0.0;
+  // voxel grid (fsdf_set_voxel_grid, fsdf_set_points_voxel, depth frames; voxel.hip): the grid is a
+  // context setting like the sensor (vox_size 0: off). voxel_cloud says the resident cloud came
+  // through it: `voxel` then holds its lists — vox_m voxels of vox_n_in input points, vox_dropped
+  // of them non-finite —, which belong to the cloud like a depth frame's pixel list.
+  double vox_size = 0.0, vox_origin[3] = {0.0, 0.0, 0.0};
+  int vox_weights = FSDF_VOXEL_COUNT;
+  bool voxel_cloud = false;
+  int64_t vox_m = 0, vox_n_in = 0, vox_dropped = 0;
+  VoxelBuffers voxel;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;
@@ -310,6 +339,13 @@ void robust_rows_finish(fsdf_ctx* c, bool moments);
 // point_weights.hip: the weights in resident order for a robust launch (null: none set), regathered
 // on the context stream when the layout changed since; whether the iteration calls take the robust path
 int point_weights_resident(fsdf_ctx* c, const double** d_conf_out);
+// voxel.hip: d_xyz [n][3] (device, fp64) through the context's grid into c->voxel (one sizing
+// synchronisation; the caller synchronised the stream before); then the weights [vox_m + tail]
+// — the counts, 1.0 per tail point — and, from a depth frame's pixel list, c->voxel.pix; and the
+// counts as the resident cloud's weights under FSDF_VOXEL_COUNT
+int voxel_downsample(fsdf_ctx* c, const double* d_xyz, int64_t n, const char* who);
+int voxel_finish(fsdf_ctx* c, int64_t tail, const int32_t* d_pix_in);
+int voxel_set_weights(fsdf_ctx* c);
 static inline bool robust_objective(const fsdf_ctx* c) {
   return c->loss_kind != FSDF_LOSS_SQUARE || c->conf_set || c->free_split >= 0;
 }

@@ -29,6 +29,8 @@
 // !(s > 0 && s < near) — and L − (double)(J − 1) · spacing > 0. Sample j sits at
 // range t = L − (double)(j − 1) · spacing: c = (t u_x, t u_y, t u_z), then p as
 // above. flash/depthsensors.py free_space_points restates it.
+//
+// depth_scan_kernel also serves voxel.hip's head-flag counts (launch_block_scan).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -216,6 +218,12 @@ static hipError_t count_scan(const void* d_depth, int64_t npix, const DepthRange
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(depth_scan_kernel, dim3(F ? 2 : 1), dim3(kScanBlock), 0, s, d_counts, (int32_t)nb, d_total);
+  return hipGetLastError();
+}
+
+hipError_t launch_block_scan(int32_t* d_counts, int rows, int32_t nblocks, int64_t* d_total, hipStream_t s) {
+  if (!d_counts || !d_total || rows < 1 || nblocks < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(depth_scan_kernel, dim3((unsigned)rows), dim3(kScanBlock), 0, s, d_counts, nblocks, d_total);
   return hipGetLastError();
 }
 

@@ -353,6 +353,17 @@ hipError_t launch_depth_count(int format, const void* d_depth, int64_t npix, con
 hipError_t launch_depth_scatter(int format, const void* d_depth, const double* d_u, int64_t npix, const DepthRange& r,
                                 const DepthPose& P, const DepthFree* free, int64_t n_surface, int64_t m,
                                 const int32_t* d_offsets, double* d_xyz, int32_t* d_pix, hipStream_t s);
+// the ingest's scan on its own (voxel.hip's head-flag counts take it too):
+// d_counts [rows][nblocks], each row's exclusive prefix in place and its total
+// to d_total [rows] — one workgroup per row, int32 sums (a row sums to < 2^31)
+hipError_t launch_block_scan(int32_t* d_counts, int rows, int32_t nblocks, int64_t* d_total, hipStream_t s);
+
+// ---- voxel-grid downsampling (voxel.hip) ------------------------------------------
+// The grid of fsdf_set_voxel_grid: cell size h (finite, > 0) and origin o; a
+// point's cell per axis is floor((x − o) / h) clamped to [−2^20, 2^20 − 1].
+struct VoxelGrid {
+  double size, origin[3];
+};
 
 // ---- second moments of RBF skins (skin_moments.hip) ----------------------------
 // Per skin r of n centres, m = 4n + 4: M_r [m][m] = Σ_{p: k*(p) = r's surface}

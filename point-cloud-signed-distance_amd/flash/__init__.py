@@ -15,7 +15,8 @@ from .robust import Huber, Tukey
 __all__ = ["BodyGeometry", "ConvexGeometry", "DeformableInterpolatingSkin", "InterpolatingGeometry",
            "Manipulator", "ManipulatorState", "RigidInterpolatingSkin", "SceneSkin", "hull_poses",
            "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError",
-           "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights", "DepthFrame", "FreeSpace"]
+           "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights", "DepthFrame", "FreeSpace",
+           "VoxelGrid"]
 
 
 def __getattr__(name):
@@ -38,6 +39,9 @@ def __getattr__(name):
     if name == "FreeSpace":  # a depth frame's free-space samples (DepthFrame(..., free_space=FreeSpace(...)))
         from .depthsensors import FreeSpace
         return FreeSpace
+    if name == "VoxelGrid":  # a world-anchored voxel grid that thins a cloud or depth frame (`voxel=`)
+        from .depthdata import VoxelGrid
+        return VoxelGrid
     if name == "DepthSensors":
         from . import depthsensors
         return depthsensors

@@ -139,6 +139,14 @@ _PROTOS = {
     "fsdf_get_free_split": (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int32)]),
     "fsdf_set_free_space": (c_int32, [c_void_p, c_int32, c_int32, c_void_p]),
     "fsdf_get_free_space": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), c_void_p]),
+    "fsdf_set_voxel_grid": (c_int32, [c_void_p, c_double, c_void_p, c_int32]),
+    "fsdf_set_voxel_grid_ref": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32]),
+    "fsdf_get_voxel_grid": (c_int32, [c_void_p, POINTER(c_double), c_void_p, POINTER(c_int32)]),
+    "fsdf_set_points_voxel": (c_int32, [c_void_p, c_void_p, c_int64]),
+    "fsdf_set_points_voxel_device": (c_int32, [c_void_p, c_void_p, c_int64]),
+    "fsdf_get_voxels": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int64),
+                                  POINTER(c_int64)]),
+    "fsdf_get_voxel_of_point": (c_int32, [c_void_p, c_void_p, POINTER(c_int64)]),
     "fsdf_set_robust_skins": (c_int32, [c_void_p, c_int32]),
     "fsdf_get_robust_skins": (c_int32, [c_void_p, POINTER(c_int32)]),
     "fsdf_eval_robust_skins": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p, c_void_p,
@@ -670,6 +678,74 @@ class Context:
         check(self._lib.fsdf_get_free_split(self._ctx, ctypes.byref(n), ctypes.byref(flag)), self._ctx,
               "get_free_split")
         return n.value if flag.value else None
+
+    def set_voxel_grid(self, grid):
+        """fsdf_set_voxel_grid: the voxel grid that set_points_voxel and every
+        later set_depth downsample through — a depthdata.VoxelGrid (anything
+        with .size, .origin, .mode), or None for off. A context setting like
+        the sensor: frames and model swaps keep it."""
+        if grid is None:
+            check(self._lib.fsdf_set_voxel_grid(self._ctx, 0.0, None, 1), self._ctx, "set_voxel_grid")
+            return
+        origin = np.ascontiguousarray(grid.origin, np.float64).reshape(-1)
+        if origin.size != 3:
+            raise ValueError(f"set_voxel_grid: the origin is 3 numbers, got {origin.size}")
+        check(self._lib.fsdf_set_voxel_grid(self._ctx, float(grid.size), ptr(origin), int(grid.mode)), self._ctx,
+              "set_voxel_grid")
+
+    def get_voxel_grid(self):
+        """fsdf_get_voxel_grid: (size, origin (3 floats), mode) as the library
+        holds them, or None when off."""
+        size, origin, mode = c_double(0.0), np.zeros(3, np.float64), c_int32(0)
+        check(self._lib.fsdf_get_voxel_grid(self._ctx, ctypes.byref(size), ptr(origin), ctypes.byref(mode)), self._ctx,
+              "get_voxel_grid")
+        return (size.value, tuple(origin.tolist()), mode.value) if size.value else None
+
+    def set_points_voxel(self, xyz: np.ndarray):
+        """fsdf_set_points_voxel: the cloud [n, 3] through the context's voxel
+        grid (set_voxel_grid) — its m centroids become the resident cloud, in
+        ascending cell-key order, then as set_points; under "count" the cells'
+        populations become the point weights. Returns m."""
+        pts = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        check(self._lib.fsdf_set_points_voxel(self._ctx, ptr(pts), pts.shape[0]), self._ctx, "set_points_voxel")
+        self.n = self._num_points()
+        return self.n
+
+    def set_points_voxel_device(self, dev_ptr: int, n: int):
+        """fsdf_set_points_voxel_device: the same from device memory."""
+        check(self._lib.fsdf_set_points_voxel_device(self._ctx, c_void_p(dev_ptr), n), self._ctx,
+              "set_points_voxel_device")
+        self.n = self._num_points()
+        return self.n
+
+    def voxel_sizes(self):
+        """fsdf_get_voxels' counters alone: (m voxels, n_in input points, dropped)."""
+        m, n_in, dropped = c_int64(0), c_int64(0), c_int64(0)
+        check(self._lib.fsdf_get_voxels(self._ctx, None, None, None, ctypes.byref(m), ctypes.byref(n_in),
+                                        ctypes.byref(dropped)), self._ctx, "get_voxels")
+        return m.value, n_in.value, dropped.value
+
+    def get_voxels(self):
+        """fsdf_get_voxels: of the resident voxel cloud (xyz [m, 3], count [m]
+        int32, cell [m, 3] int32, n_in, dropped), the voxels in caller order."""
+        m, n_in, dropped = self.voxel_sizes()
+        xyz, count, cell = np.empty((m, 3), np.float64), np.empty(m, np.int32), np.empty((m, 3), np.int32)
+        if m:
+            mm = c_int64(0)
+            check(self._lib.fsdf_get_voxels(self._ctx, ptr(xyz), ptr(count), ptr(cell), ctypes.byref(mm), None, None),
+                  self._ctx, "get_voxels")
+        return xyz, count, cell, n_in, dropped
+
+    def get_voxel_of_point(self) -> np.ndarray:
+        """fsdf_get_voxel_of_point: for every input point the caller index of
+        its voxel, −1 for a dropped (non-finite) point."""
+        n = c_int64(0)
+        check(self._lib.fsdf_get_voxel_of_point(self._ctx, None, ctypes.byref(n)), self._ctx, "get_voxel_of_point")
+        out = np.empty(n.value, np.int32)
+        if n.value:
+            check(self._lib.fsdf_get_voxel_of_point(self._ctx, ptr(out), ctypes.byref(n)), self._ctx,
+                  "get_voxel_of_point")
+        return out
 
     def eval_skin_moments(self, poses):
         """fsdf_eval_skin_moments: one pass over the resident cloud and the

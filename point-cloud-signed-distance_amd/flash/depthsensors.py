@@ -248,6 +248,22 @@ class DepthFrame:
         return free_space_points(self.depth, self.sensor.rays, self.tform, self.near, self.far, self.scale, self.kind,
                                  self.free_space)
 
+    def voxel_points(self, grid):
+        """(points [n, 3], pixels [n], weights [n]) of this frame under a
+        depthdata.VoxelGrid, the resident cloud's bits (fsdf_set_depth_* with
+        fsdf_set_voxel_grid): the observed points' voxel centroids
+        (depthdata.voxel_downsample of depth_points) followed by the free-space
+        samples unchanged; a voxel's pixel is its first point's; weights are the
+        voxels' counts, then 1.0 per sample (what the library sets under
+        "count"). points() itself stays the frame without a grid."""
+        from .depthdata import voxel_downsample
+        obs, pix = depth_points(self.depth, self.sensor.rays, self.tform, self.near, self.far, self.scale, self.kind)
+        allp, allpix = self.points()
+        xyz, count, _, first, _, _ = voxel_downsample(obs, grid)
+        tail = len(allp) - len(obs)
+        return (np.concatenate([xyz, allp[len(obs):]]), np.concatenate([pix[first], allpix[len(obs):]]).astype(np.int32),
+                np.concatenate([count.astype(np.float64), np.ones(tail)]))
+
     def n_surface(self) -> int:
         """The number of observed points (valid pixels): the samples follow them."""
         return len(depth_points(self.depth, self.sensor.rays, self.tform, self.near, self.far, self.scale,

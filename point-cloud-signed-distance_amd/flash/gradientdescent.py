@@ -119,12 +119,22 @@ class CostFunctor:
     `free_space` set sends free-space samples after the observed points
     (fsdf_set_free_space): `n_surface` is the number of observed points,
     `n_points` counts the samples too, and the objective penalises a sample
-    only where the model covers it (include/flashsdf.h "free space")."""
+    only where the model covers it (include/flashsdf.h "free space").
+    voxel (a depthdata.VoxelGrid; None: none): the cloud — of a DepthFrame its
+    observed points — is thinned on the device to one centroid per occupied
+    cell before it becomes resident (fsdf_set_points_voxel / fsdf_set_voxel_grid;
+    include/flashsdf.h "voxel grid"). `sensed_points` is then the resident
+    cloud in caller order (centroids, then a frame's samples), `n_points` its
+    size, and under weights "count" the cells' populations are the point
+    weights (`voxel_weights`: the counts, then 1.0 per sample) and `n_divisor`
+    — what the solvers divide the cost by — is their sum, the input cloud's
+    size; under "unit" it is `n_points`."""
 
     def __init__(self, manipulator: Manipulator, sensed_points, device: int = 0, precision: int = 64,
                  deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False, loss=None,
-                 robust_skins: bool = False):
+                 robust_skins: bool = False, voxel=None):
         self.manipulator = manipulator
+        self.voxel = voxel
         self.weight = deformation_cost_weight
         self.state = ManipulatorState(manipulator)
         self.ctx = manipulator.engine(device, precision)
@@ -168,18 +178,24 @@ class CostFunctor:
     def sensed_points(self):
         """The sensed cloud [n, 3] on the host; of a DepthFrame, formed on the
         first read (frame.points(): the resident cloud's bits and order)."""
+        if self.voxel is not None:  # (the resident cloud: centroids, then a frame's samples)
+            if self._voxel_points is None:
+                from .depthdata import voxel_downsample
+                self._voxel_points = voxel_downsample(self._points, self.voxel)[0] if self._frame is None \
+                    else self._frame.voxel_points(self.voxel)[0]
+            return self._voxel_points
         if self._points is None:
             self._points = self._frame.points()[0]
         return self._points
 
     @sensed_points.setter
     def sensed_points(self, points):
-        self._frame, self._points = None, points
+        self._frame, self._points, self._voxel_points = None, points, None
 
     def _take(self, sensed_points):
         # a DepthFrame as it is, anything else as the [n, 3] f64 array
         if isinstance(sensed_points, DepthFrame):
-            self._frame, self._points = sensed_points, None
+            self._frame, self._points, self._voxel_points = sensed_points, None, None
         else:
             self.sensed_points = np.ascontiguousarray(sensed_points, np.float64).reshape(-1, 3)
 
@@ -189,22 +205,43 @@ class CostFunctor:
         context's sensor is not the frame's already (by identity, like
         _mechanism_of)."""
         f = self._frame
-        if f is None:
+        if f is None and self.voxel is None:
             self.ctx.set_points(self._points)
         else:
-            have = getattr(self.ctx, "_sensor_of", None)
-            if have is None or have[0] is not f.sensor or have[1] != f.kind:
-                self.ctx._sensor_of = None
-                self.ctx.set_sensor(f.sensor.rays, f.kind)
-                self.ctx._sensor_of = (f.sensor, f.kind)
-            self.ctx.set_free_space(getattr(f, "free_space", None))  # (a context setting: this frame's)
-            self.ctx.set_depth(f.depth, f.tform, f.near, f.far, f.scale)
+            if f is not None:
+                have = getattr(self.ctx, "_sensor_of", None)
+                if have is None or have[0] is not f.sensor or have[1] != f.kind:
+                    self.ctx._sensor_of = None
+                    self.ctx.set_sensor(f.sensor.rays, f.kind)
+                    self.ctx._sensor_of = (f.sensor, f.kind)
+                self.ctx.set_free_space(getattr(f, "free_space", None))  # (a context setting: this frame's)
+            # the grid is a context setting too, and the engine is shared: set for this upload alone,
+            # so that whoever next hands the context a depth image gets the frame it asked for
+            self.ctx.set_voxel_grid(self.voxel)
+            try:
+                if f is None:
+                    self.ctx.set_points_voxel(self._points)
+                else:
+                    self.ctx.set_depth(f.depth, f.tform, f.near, f.far, f.scale)
+            finally:
+                if self.voxel is not None:
+                    self.ctx.set_voxel_grid(None)
         self.n_points = self.ctx.n
         # n_surface: the first n_surface sensed points are surface observations, the rest free-space
         # samples (a frame with free_space: the library set the split itself; a plain cloud: none
         # until set_free_split)
         split = self.ctx.get_free_split()
         self.n_surface = self.n_points if split is None else split
+        # a voxel cloud: the counts (then 1.0 per sample) and the cost's divisor — under "count" the
+        # input cloud's size (Σ count + samples), so a rate and tolerance tuned on full clouds keep
+        # their meaning; else the resident count
+        self.voxel_weights, self.n_divisor = None, self.n_points
+        if self.voxel is not None:
+            m, n_in, dropped = self.ctx.voxel_sizes()
+            if self.voxel.weights == "count":
+                self.voxel_weights = np.concatenate([self.ctx.get_voxels()[1].astype(np.float64),
+                                                     np.ones(self.n_points - m)])
+                self.n_divisor = (n_in - dropped) + (self.n_points - m)
 
     def depth_pixels(self):
         """Of a DepthFrame: pixel (row · cols + col) of every sensed point, in
@@ -230,8 +267,13 @@ class CostFunctor:
             weights = np.array(weights, np.float64, copy=True).reshape(-1)
             if len(weights) != self.n_points:
                 raise ValueError(f"point weights: {len(weights)} weights for {self.n_points} sensed points")
+            if getattr(self, "voxel_weights", None) is not None:  # (a voxel cloud under "count": times the counts)
+                weights = weights * self.voxel_weights
         self._ensure_resident()
-        self.ctx.set_point_weights(weights)  # (refused: the earlier weights stay, here too)
+        if weights is None and getattr(self, "voxel_weights", None) is not None:  # (back to the counts alone)
+            self.ctx.set_point_weights(self.voxel_weights)
+        else:
+            self.ctx.set_point_weights(weights)  # (refused: the earlier weights stay, here too)
         self.point_weights = weights
 
     def set_free_split(self, n_surface):
@@ -300,18 +342,24 @@ class CostFunctor:
     def _register_native(self):
         register_native(self.manipulator, self.ctx, self.weight)
 
-    def set_sensed_points(self, sensed_points):
+    def set_sensed_points(self, sensed_points, voxel="keep"):
         """Swap the resident cloud (a new frame): one upload + device sort; the
         functor, its state and the device model are kept. The array given to
         prefetch_sensed_points last is made resident from its device copy. A
-        depthsensors.DepthFrame is made resident from its image (set_depth)."""
+        depthsensors.DepthFrame is made resident from its image (set_depth).
+        voxel: a depthdata.VoxelGrid for this and later clouds, None for none
+        ("keep": the functor's as it is). A voxel cloud is never made resident
+        from a prefetched copy."""
         pre, src = getattr(self, "_prefetched", None), getattr(self, "_prefetched_src", None)
         self._prefetched = self._prefetched_src = None
         self.point_weights = None  # (another cloud: the library drops its copy with the old one)
-        if pre is not None and sensed_points is src:  # (the object prefetched: its device copy)
+        if not (isinstance(voxel, str) and voxel == "keep"):
+            self.voxel = voxel
+        if pre is not None and sensed_points is src and self.voxel is None:  # (the object prefetched: its device copy)
             self.sensed_points = pre
             self.ctx.set_points_prefetched()
-            self.n_points = self.n_surface = self.ctx.n
+            self.n_points = self.n_surface = self.n_divisor = self.ctx.n
+            self.voxel_weights = None
         else:
             self._take(sensed_points)
             self._upload()
@@ -354,7 +402,8 @@ class CostFunctor:
         return c + _regularizer(self.state, self.weight), accum, extras
 
     def __call__(self, x) -> float:
-        if self.loss is not None or self.point_weights is not None or self.n_surface != self.n_points:
+        if self.loss is not None or self.point_weights is not None or self.n_surface != self.n_points or \
+                getattr(self, "voxel_weights", None) is not None:
             # (the robust / weighted / split objective: the native iteration's cost)
             return self.value_and_gradient(x)[0]
         return self._pass(x)[0]

@@ -283,7 +283,8 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, l
 
 
 def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callback=None, solver=None,
-                   device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False):
+                   device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False,
+                   voxel=None):
     """Tracking.estimate_state (src/tracking.jl:8-27). Returns the solution x.
 
     The default callback accepts (x, c): the reference's default `x -> ()` is
@@ -304,16 +305,29 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
     objective penalises a sample only where the model covers it, and N in c / N
     is the resident point count, samples included (weights: one per resident
     point, samples included — CostFunctor.depth_pixels names every point's
-    pixel)."""
+    pixel).
+    voxel (a depthdata.VoxelGrid; None: none): the cloud — of a DepthFrame its
+    observed points — is thinned on the device to one centroid per occupied
+    cell (include/flashsdf.h "voxel grid"); under weights "count" the cells'
+    populations are point weights (native rigid scenes, others with
+    robust_skins), under "unit" every centroid counts 1. A weights callable
+    receives the resident points in caller order, centroids then samples, and
+    under "count" its result is multiplied by the counts. N in c / N is then
+    Σ count plus the sample count — the input cloud's size, not the number of
+    centroids —, so a rate and tolerance tuned on full clouds keep their
+    meaning; under "unit" it is the resident count."""
     solver = solver or _default_solver(manipulator)
-    if isinstance(sensed_points, DepthFrame):
+    if isinstance(sensed_points, DepthFrame) or voxel is not None:
+        if not isinstance(sensed_points, DepthFrame):
+            sensed_points = np.asarray(sensed_points, np.float64).reshape(-1, 3)
+        kw = {} if voxel is None else {"voxel": voxel}
         cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision,
-                           robust_skins=robust_skins)
+                           robust_skins=robust_skins, **kw)
         pts = lambda: cost.sensed_points  # noqa: E731 (formed when asked for)
     else:
         pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
         cost = CostFunctor(manipulator, pts, device=device, precision=precision, robust_skins=robust_skins)
-    return _optimize(cost, cost.n_points, x_estimated, callback, solver, loss=loss,
+    return _optimize(cost, getattr(cost, "n_divisor", cost.n_points), x_estimated, callback, solver, loss=loss,
                      weights=_frame_weights(weights, pts), robust_skins=robust_skins)
 
 
@@ -330,7 +344,8 @@ class Tracker:
     iteration are recorded (host FK + pass + chain rule, end to end)."""
 
     def __init__(self, manipulator: Manipulator, state: ManipulatorState | None = None, solver=None,
-                 device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False):
+                 device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False,
+                 voxel=None):
         self.manipulator = manipulator
         self.state = state if state is not None else ManipulatorState(manipulator)
         self.solver = solver or notebook_frame_solver(manipulator)
@@ -341,11 +356,12 @@ class Tracker:
         # per-point confidence weights: a callable points -> weights applied to every frame (an
         # array fits one frame only: give it to step); None: every point counts 1
         self.weights = weights
+        self.voxel = voxel  # a depthdata.VoxelGrid every frame is thinned through (None: none)
         self.frame_ms: list[float] = []
         self.set_points_ms: list[float] = []
         self.iterations: list[int] = []
 
-    def step(self, sensed_points, callback=None, next_points=None, weights=None) -> np.ndarray:
+    def step(self, sensed_points, callback=None, next_points=None, weights=None, voxel="tracker") -> np.ndarray:
         """gradient_descent!(state, model, sensed_points): one frame.
         next_points (optional): the next frame's cloud, whose upload then runs
         under this frame's solver iterations (CostFunctor.prefetch_sensed_points).
@@ -356,18 +372,27 @@ class Tracker:
         resident by the device ingest (never prefetched), and the host forms
         its points only for a weights callable. With the frame's free_space set
         the cloud holds its free-space samples after the observed points; N in
-        c / N is the resident point count, samples included."""
-        if isinstance(sensed_points, DepthFrame):
+        c / N is the resident point count, samples included.
+        voxel (optional): this frame's depthdata.VoxelGrid, or None for none;
+        by default the Tracker's own. A frame thinned through a grid is as
+        estimate_state's `voxel=`; with a grid the next cloud is not prefetched
+        (next_points is ignored)."""
+        grid = self.voxel if isinstance(voxel, str) and voxel == "tracker" else voxel
+        if isinstance(sensed_points, DepthFrame) or grid is not None:
             pts = lambda: self.cost.sensed_points  # noqa: E731 (formed when asked for)
         else:
             pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
         t0 = time.perf_counter()
-        self.cost.set_sensed_points(sensed_points)  # (the object itself: a prefetched frame is matched by identity)
-        if next_points is not None and not isinstance(next_points, DepthFrame):
+        # (the object itself: a prefetched frame is matched by identity)
+        if grid is None and getattr(self.cost, "voxel", None) is None:
+            self.cost.set_sensed_points(sensed_points)
+        else:
+            self.cost.set_sensed_points(sensed_points, voxel=grid)
+        if next_points is not None and not isinstance(next_points, DepthFrame) and grid is None:
             self.cost.prefetch_sensed_points(next_points)
         t1 = time.perf_counter()
         w = _frame_weights(self.weights if weights is None else weights, pts)
-        x = _optimize(self.cost, self.cost.n_points, flatten(self.state), callback, self.solver, loss=self.loss,
+        x = _optimize(self.cost, getattr(self.cost, "n_divisor", self.cost.n_points), flatten(self.state), callback, self.solver, loss=self.loss,
                       weights=w, robust_skins=self.robust_skins)
         unflatten(self.state, x)
         t2 = time.perf_counter()
@@ -383,7 +408,7 @@ class Tracker:
 
 
 def track(manipulator: Manipulator, frames, state: ManipulatorState | None = None, solver=None, callback=None,
-          device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False):
+          device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False, voxel=None):
     """for event in log: gradient_descent!(state, model, sensed_points)
     (examples/irb_and_squishable.ipynb cells 11-12). `frames` yields sensed
     clouds ([n,3]) or depthsensors.DepthFrames (made resident by the device
@@ -393,9 +418,13 @@ def track(manipulator: Manipulator, frames, state: ManipulatorState | None = Non
     loss: a robust point loss for every frame (flash.robust).
     weights: a callable points -> weights applied to every frame (or one array,
     where every frame has as many points).
-    robust_skins: as estimate_state's."""
+    robust_skins: as estimate_state's.
+    voxel: a depthdata.VoxelGrid every frame is thinned through (as
+    estimate_state's). With it set the next cloud is NOT prefetched — the grid
+    stage has no prefetched form —, so a frame's upload does not overlap the
+    previous frame's iterations."""
     tr = Tracker(manipulator, state, solver, device, precision, loss=loss, weights=weights,
-                 robust_skins=robust_skins)
+                 robust_skins=robust_skins, voxel=voxel)
     xs = []
     it = iter(frames)
     cur = next(it, None)
