@@ -882,6 +882,51 @@ int fsdf_get_robust_skins(const fsdf_ctx* ctx, int32_t* enable_out);
 int fsdf_eval_robust_skins(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out,
                            double* moments_out, double* skin_moments_out, double* weight_out);
 
+/* ---- scoring candidate states ------------------------------------------------------
+ * Every call that estimates a state needs a start in the right basin. To find
+ * one — a tracker's first state, or its state again after an occlusion — a
+ * caller compares many candidates, and B calls of fsdf_eval_robust cost B times
+ * the fixed price of a pass (pose, pass, robust launch, reduce, read-back) on a
+ * cloud small enough that the price is nearly all there is. These calls score
+ * B candidates against the resident cloud at once: one pose launch over
+ * (item x candidate), one score launch over (chunk group x candidate), one
+ * small launch that sums each candidate's partial sums (csrc/score.hip); a
+ * large batch runs in slices of a fixed byte budget of posed models.
+ *
+ * cost_out[b] is the objective fsdf_eval_robust puts into accum_out[0] at
+ * candidate b's poses — Σ_i a_i ρ(d*(p_i)) under the context's loss
+ * (FSDF_LOSS_SQUARE: d*²), per-point weights (1.0 without) and free-space split
+ * (a sample counts only where d* < 0) — as a sum, not a mean, with neither the
+ * prior of fsdf_set_lm_prior nor a regulariser in it. d* is the pass's, bit for
+ * bit; the terms are formed and summed in fp64 (an fp32 context's d* widened as
+ * stored) in an order that depends on the cloud's size and layout alone: no
+ * floating-point atomics, and candidate b's bits depend neither on B, nor on
+ * its place in the batch, nor on the slicing. Against fsdf_eval_robust the
+ * cost differs by summation order only (both sum the same terms).
+ *
+ * fsdf_score_poses: poses [B][S][12], each as fsdf_eval's. fsdf_score_states:
+ * x [B][nq] after fsdf_set_mechanism — the host forward kinematics and surface
+ * poses of fsdf_value_and_gradient at each x (quaternion blocks normalised),
+ * then the same path; a configuration the kinematics refuses fails the call.
+ * Both are synchronous. B = 0 is FSDF_OK and writes nothing; a cloud of no
+ * points gives exact zeros; a candidate with a non-finite pose entry gets a NaN
+ * cost and the others theirs. NULL arguments and B < 0 are FSDF_ERR_ARG.
+ * FSDF_ERR_STATE: no model, no cloud, no mechanism (fsdf_score_states), a
+ * scene with an RBF skin or a deformation, a ranged or keyed cloud, a
+ * prefetched cloud not yet made resident.
+ *
+ * The calls are read-only on the context: seeds, plan, block orders, regroup
+ * state, loss, weights and split are as before, and any later call returns the
+ * bits it returns without the scoring call.
+ *
+ * fsdf_score_time: with fsdf_profile_pass enabled a pair of events is recorded
+ * around each scoring call's launches (up to 256 pairs between queries); this
+ * synchronizes, returns their summed time and the number of calls recorded and
+ * resets the record, as fsdf_skin_moments_time. */
+int fsdf_score_poses(fsdf_ctx* ctx, const double* poses /* [B][S][12] */, int32_t B, double* cost_out /* [B] */);
+int fsdf_score_states(fsdf_ctx* ctx, const double* x /* [B][nq] */, int32_t B, double* cost_out /* [B] */);
+int fsdf_score_time(fsdf_ctx* ctx, double* total_ms_out, int64_t* launches_out);
+
 /* ---- context ---------------------------------------------------------------- */
 int fsdf_create(fsdf_ctx** out, const fsdf_opts* opts);
 int fsdf_destroy(fsdf_ctx* ctx);

@@ -439,6 +439,40 @@ function eval_robust_skins(ctx::Context, poses::Vector{Float64})
 end
 
 """
+Score B candidate pose sets against the resident cloud in one batch of launches (fsdf_score_poses):
+poses is 12 x S x B (each candidate as eval_robust takes it); returns the B costs — eval_robust's
+cost at each candidate under the context's loss, weights and split, as a sum, with no gradient.
+Hull-only scenes; read-only on the context.
+"""
+function score_poses(ctx::Context, poses::Array{Float64}, B::Integer)
+    cost = zeros(B)
+    check(ctx.ptr, ccall((:fsdf_score_poses, lib), Cint, (Ptr{Void}, Ptr{Float64}, Int32, Ptr{Float64}),
+                         ctx.ptr, poses, Int32(B), cost), "score_poses")
+    cost
+end
+
+"""
+score_poses from states (fsdf_score_states): x is nq x B; the library runs its own forward
+kinematics per candidate, so the context needs a mechanism registered through the C interface
+(fsdf_set_mechanism; this shim keeps RigidBodyDynamics and registers none: FSDF_ERR_STATE).
+"""
+function score_states(ctx::Context, x::Array{Float64}, B::Integer)
+    cost = zeros(B)
+    check(ctx.ptr, ccall((:fsdf_score_states, lib), Cint, (Ptr{Void}, Ptr{Float64}, Int32, Ptr{Float64}),
+                         ctx.ptr, x, Int32(B), cost), "score_states")
+    cost
+end
+
+"(summed milliseconds of the scoring calls' launches, calls recorded) since the last query (fsdf_score_time)."
+function score_time(ctx::Context)
+    ms = Ref{Float64}(0)
+    n = Ref{Int64}(0)
+    check(ctx.ptr, ccall((:fsdf_score_time, lib), Cint, (Ptr{Void}, Ref{Float64}, Ref{Int64}), ctx.ptr, ms, n),
+          "score_time")
+    ms[], n[]
+end
+
+"""
 Per-point confidence weights a_i >= 0 (finite) of the resident cloud, in the order of the points
 given to set_points! (fsdf_set_point_weights): every sum of eval_robust carries a_i as a factor
 of point i's terms (cost Σ a ρ, wrench Σ 2 a w d* v, moments Σ a w v vᵀ). They belong to the

@@ -571,6 +571,7 @@ extern "C" int fsdf_profile_pass(fsdf_ctx* c, int32_t enable) {
   c->profiling = enable != 0;
   c->prof_used = 0;
   c->skin_ev_used = 0;
+  c->score_ev_used = 0;  // (fsdf_score_time's pairs: created by the first profiled scoring call)
   return FSDF_OK;
 }
 

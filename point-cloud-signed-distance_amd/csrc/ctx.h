@@ -243,6 +243,15 @@ struct fsdf_ctx {
   bool voxel_cloud = false;
   int64_t vox_m = 0, vox_n_in = 0, vox_dropped = 0;
   VoxelBuffers voxel;
+  // scoring candidate states (fsdf_score_poses, fsdf_score_states; score_api.hip over score.hip): the
+  // batch's poses [B][S][12] and costs [B] on the device and pinned, one slice's posed tables and
+  // partials; buffers of their own — a scoring call writes nothing any other call reads. Timing
+  // (fsdf_score_time): a pair of events per profiled call, created on first use.
+  fsdf::DevBuf<double> score_poses, score_partials, score_cost;
+  fsdf::DevBuf<unsigned char> score_tables;
+  fsdf::PinnedBuf<double> h_score_poses, h_score_cost;
+  std::vector<fsdf::Event> score_ev;
+  size_t score_ev_used = 0;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;

@@ -316,6 +316,33 @@ hipError_t launch_robust_skin(int precision, const void* d_pts, const int32_t* d
                               const void* d_rows, const LocalModel& lm, const double* d_conf, const int32_t* d_perm,
                               int64_t n_surface, int64_t n, int kind, double scale, double* d_partials,
                               double* d_blocks, hipStream_t s);
+// ---- scoring candidate states (score.hip) -----------------------------------------
+// B candidates' posed models side by side: candidate b's table lies b · stride
+// bytes into the buffer — world planes [F][4] T, world vertices [V][4] T, the
+// hull table [K+1] HullRow and (f64) the fp32 screening pairs [F+K][4], each at
+// its byte offset (multiples of 256). score_table is a function of (precision,
+// model) alone.
+struct ScoreTable {
+  size_t stride = 0, planes = 0, verts = 0, rows = 0, screen = 0;
+};
+ScoreTable score_table(int precision, const LocalModel& lm);
+constexpr int kScoreBlock = 256;      // 4 waves, a 64-point chunk each per round
+constexpr int kScoreMaxGroups = 512;  // workgroups per candidate, at most (grid-stride beyond)
+// workgroups per candidate for a cloud of n points: a function of n alone
+int score_groups(int64_t n);
+// hull-only scenes of up to kMaxHulls hulls whose table and stages fit a workgroup's LDS
+bool score_fits(const LocalModel& lm);
+// d_poses [B][S][12] -> d_tables [B] tables (pose_impl.h pose_item per candidate); B <= 65535
+hipError_t launch_score_pose(int precision, const LocalModel& lm, const double* d_poses, int B, void* d_tables,
+                             hipStream_t s);
+// d_cost[b] = Σ_i a_i ρ(d*_b(p_i)) over the resident cloud d_pts (context
+// precision; terms and sums fp64) against table b: n > 0, score_fits(lm), a
+// valid loss. d_chunk_ws: null, or the resident chunk spheres; d_conf, d_perm,
+// n_surface as launch_robust's. d_partials [B][score_groups(n)]. Two launches.
+hipError_t launch_score(int precision, bool cull, const LocalModel& lm, const void* d_tables, const void* d_pts,
+                        int64_t n, int B, const float* d_chunk_ws, const double* d_conf, const int32_t* d_perm,
+                        int64_t n_surface, int kind, double scale, double* d_partials, double* d_cost,
+                        hipStream_t s);
 // res[i] = src[perm[i]] over n doubles (point_weights.hip: a per-point side array
 // into resident order; an index outside [0, n) reads as 0)
 hipError_t launch_gather_f64(const double* d_src, const int32_t* d_perm, int64_t n, double* d_res, hipStream_t s);

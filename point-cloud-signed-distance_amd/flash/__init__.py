@@ -16,7 +16,7 @@ __all__ = ["BodyGeometry", "ConvexGeometry", "DeformableInterpolatingSkin", "Int
            "Manipulator", "ManipulatorState", "RigidInterpolatingSkin", "SceneSkin", "hull_poses",
            "num_deformations", "num_states", "skin", "surfaces", "Models", "FlashNativeError",
            "LevenbergMarquardt", "Huber", "Tukey", "depth_noise_weights", "DepthFrame", "FreeSpace",
-           "VoxelGrid"]
+           "VoxelGrid", "multi_start", "candidates_around"]
 
 
 def __getattr__(name):
@@ -30,6 +30,9 @@ def __getattr__(name):
     if name == "LevenbergMarquardt":  # the opt-in second-order tracking solver
         from .tracking import LevenbergMarquardt
         return LevenbergMarquardt
+    if name in ("multi_start", "candidates_around"):  # a start found by scoring many candidates at once
+        from . import tracking
+        return getattr(tracking, name)
     if name == "depth_noise_weights":  # per-point confidence weights from a depth sensor's axial noise
         from .depthsensors import depth_noise_weights
         return depth_noise_weights

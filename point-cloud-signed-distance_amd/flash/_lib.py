@@ -151,6 +151,9 @@ _PROTOS = {
     "fsdf_get_robust_skins": (c_int32, [c_void_p, POINTER(c_int32)]),
     "fsdf_eval_robust_skins": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "fsdf_score_poses": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "fsdf_score_states": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
+    "fsdf_score_time": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -511,6 +514,34 @@ class Context:
               self._ctx, "eval_robust")
         return cost.value, accum, mom, wts
 
+    def score_poses(self, poses):
+        """fsdf_score_poses: poses [B, K, 12] (or [B, K, 3, 4]) -> costs [B],
+        the objective eval_robust returns at each (the context's loss, weights
+        and split; a sum, no prior, no regulariser), all candidates in one
+        batch of launches. Hull-only scenes; read-only on the context."""
+        p = np.ascontiguousarray(poses, np.float64)
+        if p.size % (12 * max(self.K, 1)) != 0:
+            raise ValueError(f"score_poses: expected [B, {self.K}, 12] poses, got shape {p.shape}")
+        B = p.size // (12 * max(self.K, 1))
+        cost = np.empty(B, np.float64)
+        check(self._lib.fsdf_score_poses(self._ctx, ptr(p), B, ptr(cost)), self._ctx, "score_poses")
+        return cost
+
+    def score_states(self, X):
+        """fsdf_score_states: states [B, nq] -> costs [B] (set_mechanism first;
+        host FK per candidate as value_and_gradient's, then score_poses' path)."""
+        x = np.ascontiguousarray(X, np.float64)
+        nq = getattr(self, "nq", 0)
+        nx = nq + 3 * getattr(self, "n_deform", 0)  # (a deformable scene's rows: the library refuses them itself)
+        if x.ndim == 1 and nx:
+            x = x.reshape(-1, nx)
+        if nq and (x.ndim != 2 or x.shape[1] != nx):
+            raise ValueError(f"score_states: X must be [B, {nx}], got shape {x.shape}")
+        B = x.shape[0] if x.ndim == 2 else 0
+        cost = np.empty(B, np.float64)
+        check(self._lib.fsdf_score_states(self._ctx, ptr(x), B, ptr(cost)), self._ctx, "score_states")
+        return cost
+
     def set_point_weights(self, weights):
         """fsdf_set_point_weights: one confidence weight a_i >= 0 (finite) per
         resident point, in the order of the array the cloud was set from
@@ -860,6 +891,13 @@ class Context:
         ms, n = c_double(0.0), c_int64(0)
         check(self._lib.fsdf_skin_moments_time(self._ctx, ctypes.byref(ms), ctypes.byref(n)), self._ctx,
               "skin_moments_time")
+        return ms.value, n.value
+
+    def score_time(self):
+        """(summed milliseconds of the scoring calls' launches, the calls
+        recorded) since the last query (profile_pass on)."""
+        ms, n = c_double(0.0), c_int64(0)
+        check(self._lib.fsdf_score_time(self._ctx, ctypes.byref(ms), ctypes.byref(n)), self._ctx, "score_time")
         return ms.value, n.value
 
     def pass_times(self):

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .core import ConvexGeometry, InterpolatingGeometry, Manipulator, ManipulatorState, prepare_pass
+from .core import ConvexGeometry, InterpolatingGeometry, Manipulator, ManipulatorState, num_states, prepare_pass
 from .depthsensors import DepthFrame
 
 default_deformation_cost_weight = 10
@@ -420,6 +420,29 @@ class CostFunctor:
             return self.ctx.value_and_gradient(x)
         c, accum, _ = self._pass(x)
         return c, gradient_from_accum(self.manipulator, x, accum, self._solves, self.weight)
+
+    def score(self, X) -> np.ndarray:
+        """The objective at many candidate states in one batch of launches
+        (fsdf_score_states, csrc/score.hip): X is [B, n_states], or a list of
+        ManipulatorState; returns the costs [B] — value_and_gradient's cost at
+        each row (the functor's loss, weights and split; Σ, not Σ/N), to
+        summation order, with no gradient. Native rigid scenes; the others are
+        refused with the library's error. Read-only on the resident cloud: a
+        later evaluation returns the bits it returns without the call."""
+        if not self._native:
+            raise NotImplementedError("score: scene is not native-capable")
+        if isinstance(X, (list, tuple)) and len(X) and isinstance(X[0], ManipulatorState):
+            X = [flatten(s) for s in X]
+        X = np.ascontiguousarray(X, np.float64)
+        if X.ndim == 1:
+            X = X.reshape(1, -1) if X.size else X.reshape(0, num_states(self.manipulator))
+        if X.ndim != 2 or X.shape[1] != num_states(self.manipulator):
+            raise ValueError(f"score: X must be [B, {num_states(self.manipulator)}], got shape {X.shape}")
+        self._ensure_resident()
+        if getattr(self.ctx, "_mechanism_of", None) != (self.manipulator, self.weight):
+            self._register_native()
+        self._assert_loss()
+        return self.ctx.score_states(X)
 
     def descend(self, x, iteration_limit, rate, max_step, tolerance=0.0, divisors=None, n_points=1.0):
         """The NaiveSolver loop over value_and_gradient in one native call

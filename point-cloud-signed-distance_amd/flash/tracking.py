@@ -331,6 +331,114 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
                      weights=_frame_weights(weights, pts), robust_skins=robust_skins)
 
 
+def candidates_around(manipulator: Manipulator, x, sigma, count: int, seed=0) -> np.ndarray:
+    """`count` candidate states around x for multi_start: x itself first, then
+    count − 1 Gaussian perturbations x + σ ∘ z, z ~ N(0, I) drawn row by row
+    from numpy.random.default_rng(seed) — the same rows for the same seed.
+    sigma is a scalar or one value per coordinate of the state (>= 0, finite);
+    every quaternion block of every row, x's included, is renormalised
+    (Mechanism.normalize). Returns [count, n_states]."""
+    n = num_states(manipulator)
+    x = np.array(x, np.float64, copy=True).reshape(-1)
+    if x.size != n:
+        raise ValueError(f"candidates_around: x must have {n} entries, got {x.size}")
+    count = int(count)
+    if count < 1:
+        raise ValueError(f"candidates_around: count must be >= 1, got {count}")
+    sig = np.asarray(sigma, np.float64)
+    if sig.ndim > 1 or (sig.ndim == 1 and sig.size != n):
+        raise ValueError(f"candidates_around: sigma must be a scalar or have {n} entries")
+    if not (np.all(np.isfinite(sig)) and np.all(sig >= 0.0)):
+        raise ValueError("candidates_around: sigma must be finite and >= 0")
+    rng = np.random.default_rng(seed)
+    X = np.empty((count, n))
+    X[0] = x
+    if count > 1:
+        X[1:] = x + np.broadcast_to(sig, (n,)) * rng.standard_normal((count - 1, n))
+    nq = manipulator.mechanism.num_positions
+    for row in X:
+        row[:nq] = manipulator.mechanism.normalize(row[:nq])
+    return X
+
+
+def select_candidates(scores, keep: int) -> np.ndarray:
+    """multi_start's selection rule: the indices of the `keep` lowest scores,
+    best first. A NaN score ranks after every number (NaN last), equal scores
+    rank by lower index; keep above the number of scores keeps them all."""
+    s = np.asarray(scores, np.float64).reshape(-1)
+    keep = int(keep)
+    if keep < 1:
+        raise ValueError(f"multi_start: keep must be >= 1, got {keep}")
+    order = sorted(range(s.size), key=lambda i: (bool(np.isnan(s[i])), 0.0 if np.isnan(s[i]) else float(s[i]), i))
+    return np.array(order[:keep], np.int64)
+
+
+def _multi_start_on(cost, n_points: int, candidates, keep, solver, callback):
+    """multi_start over a functor whose cloud is resident and whose loss and
+    weights are set: score, select, refine each kept candidate with _optimize,
+    return the refined state of least final objective (ties: the better-scored
+    candidate; a NaN objective last)."""
+    X = np.ascontiguousarray(candidates, np.float64)
+    if X.ndim != 2 or X.shape[0] < 1:
+        raise ValueError(f"multi_start: candidates must be [B >= 1, n_states], got shape {X.shape}")
+    scores = np.asarray(cost.score(X), np.float64).reshape(-1)
+    if scores.size != X.shape[0]:
+        raise ValueError(f"multi_start: {scores.size} scores for {X.shape[0]} candidates")
+    kept = select_candidates(scores, keep)
+    refined, refined_costs = [], []
+    for b in kept:
+        x = _optimize(cost, n_points, X[b], callback, solver)
+        refined.append(np.asarray(x, np.float64))
+        refined_costs.append(float(cost(x)))
+    refined_costs = np.array(refined_costs, np.float64)
+    j = int(select_candidates(refined_costs, 1)[0])
+    info = {"scores": scores, "kept": kept, "refined_costs": refined_costs, "chosen": int(kept[j]),
+            "refined": np.array(refined)}
+    return refined[j], info
+
+
+def multi_start(manipulator: Manipulator, sensed_points, candidates, keep: int = 1, solver=None, loss=None,
+                weights=None, voxel=None, device: int = 0, precision: int = 64, callback=None):
+    """A start in the right basin, found rather than given: score every
+    candidate state against the cloud in one batch of launches
+    (CostFunctor.score, fsdf_score_states), keep the `keep` lowest, refine each
+    with estimate_state's own path (_optimize on the same CostFunctor: one
+    upload for everything) and return (x, info): the refined state of least
+    final objective and
+      info["scores"]        [B] the candidates' objectives (Σ, not Σ/N)
+      info["kept"]          indices of the candidates refined, best score first
+      info["refined_costs"] [keep] the objective at each refined state
+      info["chosen"]        the index of the candidate whose refinement won
+      info["refined"]       [keep, n_states] the refined states
+    Selection rule (select_candidates): NaN ranks last, equal values by lower
+    index — for the scores and for the refined costs (in `kept` order) alike.
+    sensed_points, loss, weights, voxel, device, precision, callback and solver
+    are estimate_state's (a DepthFrame and a VoxelGrid included); candidates is
+    [B, n_states] (candidates_around draws them). Native rigid scenes."""
+    solver = solver or _default_solver(manipulator)
+    X = np.ascontiguousarray(candidates, np.float64)
+    if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] != num_states(manipulator):
+        raise ValueError(f"multi_start: candidates must be [B >= 1, {num_states(manipulator)}], got shape {X.shape}")
+    if int(keep) < 1:
+        raise ValueError(f"multi_start: keep must be >= 1, got {keep}")
+    if isinstance(sensed_points, DepthFrame) or voxel is not None:
+        if not isinstance(sensed_points, DepthFrame):
+            sensed_points = np.asarray(sensed_points, np.float64).reshape(-1, 3)
+        kw = {} if voxel is None else {"voxel": voxel}
+        cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision, **kw)
+        pts = lambda: cost.sensed_points  # noqa: E731 (formed when asked for)
+    else:
+        pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
+        cost = CostFunctor(manipulator, pts, device=device, precision=precision)
+    # (the objective the candidates are scored under is the one they are refined under)
+    if loss is not None:
+        cost.set_loss(loss)
+    w = _frame_weights(weights, pts)
+    if w is not None:
+        cost.set_point_weights(w)
+    return _multi_start_on(cost, getattr(cost, "n_divisor", cost.n_points), X, keep, solver, callback)
+
+
 def notebook_frame_solver(manipulator):
     """gradient_descent!'s solver (examples/irb_and_squishable.ipynb cell 11)."""
     return NaiveSolver(num_states(manipulator), rate=0.5, max_step=0.1, iteration_limit=1)
@@ -400,6 +508,39 @@ class Tracker:
         self.frame_ms.append((t2 - t0) * 1e3)
         self.iterations.append(getattr(self.solver, "iterations", 0))
         return x
+
+    def relocalize(self, sensed_points, candidates=None, sigma=0.3, count: int = 64, keep: int = 2, seed=0,
+                   solver=None, callback=None, weights=None, voxel="tracker"):
+        """Find the state again (a first frame, or after an occlusion or a
+        dropped frame): make the frame's cloud resident as step does, run
+        multi_start's search on the Tracker's own CostFunctor around its current
+        state — candidates, or candidates_around(state, sigma, count, seed) —
+        and adopt the result. Returns (x, info) as multi_start. solver: the
+        refinement's solver (default: estimate_state's, 30 iterations; the
+        Tracker's own frame solver takes single steps). step itself never calls
+        this: recovery is the caller's decision."""
+        grid = self.voxel if isinstance(voxel, str) and voxel == "tracker" else voxel
+        if isinstance(sensed_points, DepthFrame) or grid is not None:
+            pts = lambda: self.cost.sensed_points  # noqa: E731 (formed when asked for)
+        else:
+            pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
+        if grid is None and getattr(self.cost, "voxel", None) is None:
+            self.cost.set_sensed_points(sensed_points)
+        else:
+            self.cost.set_sensed_points(sensed_points, voxel=grid)
+        if candidates is None:
+            candidates = candidates_around(self.manipulator, flatten(self.state), sigma, count, seed)
+        if self.robust_skins:
+            self.cost.set_robust_skins(True)
+        if self.loss is not None:
+            self.cost.set_loss(self.loss)
+        w = _frame_weights(self.weights if weights is None else weights, pts)
+        if w is not None:
+            self.cost.set_point_weights(w)
+        x, info = _multi_start_on(self.cost, getattr(self.cost, "n_divisor", self.cost.n_points), candidates, keep,
+                                  solver or _default_solver(self.manipulator), callback)
+        unflatten(self.state, x)
+        return x, info
 
     def iteration_ms(self) -> float:
         """Mean end-to-end milliseconds per solver iteration (excluding the cloud swap)."""
