@@ -882,6 +882,49 @@ int fsdf_get_robust_skins(const fsdf_ctx* ctx, int32_t* enable_out);
 int fsdf_eval_robust_skins(fsdf_ctx* ctx, const double* poses, double* cost_out, double* accum_out,
                            double* moments_out, double* skin_moments_out, double* weight_out);
 
+/* ---- robust objectives on the device solver loops ----------------------------------
+ * With a robust objective (a loss other than SQUARE, point weights, or a free
+ * split) the solver loops above run on the host: fsdf_set_solver 1 and
+ * fsdf_set_lm_solver 1 take the host loop, the required modes are refused.
+ * fsdf_set_robust_loops (a context setting like fsdf_set_robust_skins;
+ * enable = 0, the default, leaves every such answer as it is — the same
+ * status, message and bits; other values than 0 / 1 are FSDF_ERR_ARG) admits
+ * the robust objective to the device-resident loops of fsdf_descend and
+ * fsdf_descend_lm on hull-only rigid scenes of at most 282 surfaces. What
+ * fsdf_set_solver and fsdf_set_lm_solver say is unchanged — where the loop
+ * runs; this switch says whether a robust objective may run there. With
+ * enable = 1: modes 1 take the device loop where it fits (resident points, the
+ * solver kernels' LDS, for LM a damping > 0) and the host loop otherwise; the
+ * required modes (fsdf_set_solver 2, fsdf_set_lm_solver 2) succeed where it
+ * fits and answer FSDF_ERR_STATE with the reason where it does not. Scenes
+ * with RBF skins or deformations (fsdf_set_robust_skins, fsdf_set_solver
+ * 3 / 4) keep the host loop under a robust objective and their required modes
+ * stay refused: the robust device loops do not serve them.
+ *
+ * Per evaluation the pass writes k*, d* and ∇d* in resident order, the robust
+ * launch (csrc/robust.hip) reduces them per surface, an assembly launch forms
+ * the accumulator [1 + 6S] (Σρ summed over the surfaces in ascending order
+ * from 0.0) and the moments [S][21] from the rows on the device — the
+ * arithmetic the host does after its read-back — and the unchanged step
+ * kernels read those. All three return at once on the evaluations a finished
+ * frame still has queued. After the first evaluation's regroup the loop reads
+ * the regrouped layout's permutation and weights, as the host loop's second
+ * evaluation does. x, the value, the evaluation count and the final damping
+ * are bit-identical to the host loop's on the same context state.
+ *
+ * fsdf_eval_robust_device: the asynchronous twin of fsdf_eval_robust, as
+ * fsdf_eval_device is of fsdf_eval, and needs no switch. The pass, the robust
+ * launch and the assembly are enqueued on the context stream and the call
+ * returns: d_accum [1 + 6S] and d_moments [S][21] (NULL: the rows of 8, no
+ * moments) are device memory, fsdf_eval_robust's accum_out and moments_out bit
+ * for bit once the stream reaches them. Hull-only scenes (an RBF skin or a
+ * deformation: FSDF_ERR_STATE); a cloud of no points gives zeros. It never
+ * regroups. */
+int fsdf_set_robust_loops(fsdf_ctx* ctx, int32_t enable);
+int fsdf_get_robust_loops(const fsdf_ctx* ctx, int32_t* enable_out);
+int fsdf_eval_robust_device(fsdf_ctx* ctx, const double* poses, double* d_accum /* [1 + 6S], device */,
+                            double* d_moments /* [S][21], device, or NULL */);
+
 /* ---- scoring candidate states ------------------------------------------------------
  * Every call that estimates a state needs a start in the right basin. To find
  * one — a tracker's first state, or its state again after an occlusion — a

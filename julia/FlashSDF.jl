@@ -439,6 +439,34 @@ function eval_robust_skins(ctx::Context, poses::Vector{Float64})
 end
 
 """
+Let a robust objective (a loss, point weights, a free-space split) run on the device-resident solver
+loops of fsdf_descend / fsdf_descend_lm (fsdf_set_robust_loops; hull-only rigid scenes, the host
+loop's bits). Off by default: such objectives take the host loop and the required modes are refused.
+"""
+set_robust_loops!(ctx::Context, enable::Bool) =
+    check(ctx.ptr, ccall((:fsdf_set_robust_loops, lib), Cint, (Ptr{Void}, Int32), ctx.ptr, Int32(enable)),
+          "set_robust_loops")
+
+"The switch as the library holds it (fsdf_get_robust_loops)."
+function get_robust_loops(ctx::Context)
+    v = Ref{Int32}(0)
+    check(ctx.ptr, ccall((:fsdf_get_robust_loops, lib), Cint, (Ptr{Void}, Ref{Int32}), ctx.ptr, v),
+          "get_robust_loops")
+    v[] != 0
+end
+
+"""
+eval_robust without its synchronisation and read-back (fsdf_eval_robust_device): the pass, the robust
+launch and the rows' assembly are enqueued on the context stream; d_accum (1 + 6S doubles) and
+d_moments (21 x S doubles, or C_NULL for none) are device pointers, filled with eval_robust's bits.
+"""
+eval_robust_device(ctx::Context, poses::Vector{Float64}, d_accum::Ptr{Float64},
+                   d_moments::Ptr{Float64}=Ptr{Float64}(C_NULL)) =
+    check(ctx.ptr, ccall((:fsdf_eval_robust_device, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.ptr, poses, d_accum, d_moments), "eval_robust_device")
+
+"""
 Score B candidate pose sets against the resident cloud in one batch of launches (fsdf_score_poses):
 poses is 12 x S x B (each candidate as eval_robust takes it); returns the B costs — eval_robust's
 cost at each candidate under the context's loss, weights and split, as a sum, with no gradient.

@@ -201,6 +201,12 @@ struct fsdf_ctx {
   fsdf::DevBuf<double> robust_partials, robust_rows;
   fsdf::PinnedBuf<double> h_robust;
   std::vector<double> robust_accum, robust_moments;  // the accumulator (fsdf_eval's layout) and moments [S][21] from the rows
+  // the device solver loops on a robust objective (fsdf_set_robust_loops: a context setting like
+  // robust_skins, off by default; descend.hip): the accumulator [1 + 6S] and moments [S][21]
+  // assembled from the rows on the device (robust.hip robust_assemble_kernel), which the step
+  // kernels read in place of the pass's least-squares accumulator and the moments kernel's sums
+  int robust_loops = 0;
+  fsdf::DevBuf<double> robust_dev_accum, robust_dev_moments;
   // robust objectives on RBF skins and deformations (fsdf_set_robust_skins: a context setting like
   // lm_skins; robust_skin.hip): the workgroups' partials, the skins' blocks [rbf_acc], their pinned
   // read-back. The weighted skin moments reuse skin_partials / skin_moments / h_skin_moments.

@@ -176,6 +176,10 @@ static int descend_checks(fsdf_ctx* c, const char* who, const double* x, int32_t
 // (FK of x0 -> poses), then per iteration pose -> pass -> reduce -> solver
 // step, all enqueued up front; one read-back of x, f and the count at the end.
 // Bit-identical to the host loop below (solver.hip).
+// Under a robust objective (fsdf_set_robust_loops, rigid scenes): pose -> pass
+// (k*, d*, ∇d*) -> reduce -> robust sums -> their reduce -> assembly -> solver
+// step; the regrouped layout's permutation and weights are read again after the
+// first evaluation's regroup, where the host loop's next evaluation gets them.
 static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, double rate, double max_step,
                           double tolerance, const double* divisors, double n_points, double* value_out,
                           int32_t* iterations_out) {
@@ -194,6 +198,34 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
   HIPCHECK(c, c->solver.reserve(need));
   HIPCHECK(c, c->solver_flags.reserve(4));
   HIPCHECK(c, c->h_solver.reserve(hs.total));
+  // A robust objective (fsdf_set_robust_loops; fsdf_descend admits rigid scenes alone): the pass
+  // also writes k*, d*, ∇d* in resident order, the robust launch (robust.hip, rows of 8) sums
+  // them and the assembly writes the accumulator the step reads — in place of the pass's own,
+  // which still goes to c->model.accum. The rule of device_buffers.h: reserved here, the
+  // pointers read below, the launches take the locals.
+  const bool robust = robust_objective(c);
+  const int64_t n = c->n;
+  const int S = c->lm.S;
+  if (robust) {
+    const int rc = ensure_outputs(c, n);
+    if (rc) return rc;
+    HIPCHECK(c, c->robust_partials.reserve(fsdf::robust_partials_len(n, S)));
+    HIPCHECK(c, c->robust_rows.reserve((size_t)S * fsdf::kRobustLen));
+    HIPCHECK(c, c->robust_dev_accum.reserve((size_t)1 + 6 * (size_t)S));
+  }
+  int32_t* d_kstar = robust ? c->kstar.get() : nullptr;
+  double* d_d = robust ? c->d.get() : nullptr;
+  double* d_grad = robust ? c->grad.get() : nullptr;
+  double* d_rpartials = c->robust_partials.get();
+  double* d_rows = c->robust_rows.get();
+  double* d_step_accum = robust ? c->robust_dev_accum.get() : c->model.accum.get();
+  const int32_t* d_perm = c->cur.perm.get();
+  // (the per-point weights in resident order, regathered when the layout changed since; null: none set)
+  const double* d_conf = nullptr;
+  if (robust) {
+    const int rc = point_weights_resident(c, &d_conf);
+    if (rc) return rc;
+  }
   double* h = c->h_solver.get();
   double* d_solver = c->solver.get();
   HIPCHECK(c, hipStreamSynchronize(c->stream));  // (the pinned staging of an earlier frame is free)
@@ -224,15 +256,26 @@ static int descend_device(fsdf_ctx* c, double* x, int32_t iteration_limit, doubl
   if (T.R > 0) c->rbf_ready = true;
   HOST_STAMP(0);
   for (int it = 0; it < iteration_limit; ++it) {
-    int rc = run_pass(c, nullptr, c->cur.pts.get(), c->n, c->model.accum.get(), nullptr, nullptr, nullptr, nullptr,
+    int rc = run_pass(c, nullptr, c->cur.pts.get(), c->n, c->model.accum.get(), d_kstar, d_d, d_grad, nullptr,
                       true, true, st.flags);
     if (rc) return rc;
+    if (robust) {  // (before the regroup: the launch reads the layout the pass ran on)
+      HIPCHECK(c, fsdf::launch_robust(c->precision, false, c->cur.pts.get(), d_kstar, d_d, d_grad, d_conf, d_perm,
+                                      c->free_split, n, S, c->loss_kind, c->loss_scale, d_rpartials, d_rows,
+                                      c->stream, st.flags));
+      HIPCHECK(c, fsdf::launch_robust_assemble(false, d_rows, c->lm.surface_kind, S, d_step_accum, nullptr,
+                                               c->stream, st.flags));
+    }
     if (it == 0) {
       rc = iteration_regroup(c);
       if (rc) return rc;
+      if (robust) {  // (the regrouped layout's permutation and weights, as the host loop's next evaluation)
+        d_perm = c->cur.perm.get();
+        rc = point_weights_resident(c, &d_conf);
+        if (rc) return rc;
+      }
     }
-    HIPCHECK(c, fsdf::launch_solver_step(c->stree, st, c->model.accum.get(), c->lm, c->pm, c->precision, it,
-                                         c->stream));
+    HIPCHECK(c, fsdf::launch_solver_step(c->stree, st, d_step_accum, c->lm, c->pm, c->precision, it, c->stream));
   }
   HOST_STAMP(1);
   HIPCHECK(c, hipMemcpyAsync(h, st.x, (size_t)2 * nx * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -300,8 +343,21 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
   // A loss other than SQUARE (fsdf_set_loss) is served by the host loop alone
   // (the device step reads the pass's least-squares accumulator).
   // Per-point weights (fsdf_set_point_weights) and a free-space split (fsdf_set_free_split) likewise.
+  // fsdf_set_robust_loops admits them to the device loop on hull-only rigid scenes whose robust
+  // table fits (descend_device: the robust launch and the assembly feed the step); scenes with RBF
+  // skins or deformations keep the host loop under a robust objective (modes 3 / 4 as well).
   const bool loss = robust_objective(c);
-  if (loss && required && iteration_limit > 0)
+  // (robust_fit holds up to 282 surfaces and fsdf_set_surfaces admits 256: with that limit the
+  // table always fits, and the refusal that names it below is not reachable today)
+  const bool robust_dev = loss && c->robust_loops && rigid && fsdf::robust_fit(c->lm.S);
+  if (loss && !robust_dev && c->robust_loops && required && iteration_limit > 0)
+    return fail(c, FSDF_ERR_STATE,
+                "descend: the device loop was required (fsdf_set_solver %d) under a robust objective "
+                "(fsdf_set_robust_loops) but the scene %s",
+                c->solver_device,
+                !rigid ? "has RBF skins / deformations (the robust device loops serve hull-only rigid scenes)" :
+                         "has more surfaces than the robust table's LDS holds (at most 282)");
+  if (loss && !robust_dev && required && iteration_limit > 0)
     return fail(c, FSDF_ERR_STATE,
                 "descend: the device loop was required (fsdf_set_solver %d) but %s (the host loop serves it)",
                 c->solver_device,
@@ -310,7 +366,7 @@ extern "C" int fsdf_descend(fsdf_ctx* c, double* x, int32_t iteration_limit, dou
                 c->loss_kind == FSDF_LOSS_HUBER ? "a loss is set (fsdf_set_loss kind 1)" :
                                                   "a loss is set (fsdf_set_loss kind 2)");
   bool device_loop = c->solver_device && iteration_limit > 0 && (rigid || (c->solver_device >= 3 && declared)) &&
-                     c->n > 0 && !loss;
+                     c->n > 0 && (!loss || robust_dev);
   if (device_loop && !c->solver_tree_ok) {
     HIPCHECK(c, hipSetDevice(c->device));
     const int rc = build_solver_tree(c);
@@ -447,6 +503,13 @@ extern "C" int fsdf_set_lm_skins(fsdf_ctx* c, int32_t enable) {
 // (2) their pointers are read into locals; (3) the launches take the locals.
 // The cloud pointer alone is read again after the first evaluation's regroup,
 // which swaps the resident cloud's buffer (sort.hip regroup_points).
+// Under a robust objective (fsdf_set_robust_loops): the pass also writes d*, the
+// robust launch (robust.hip, rows of 29) stands where the moments launch does,
+// and the assembly writes an accumulator and moments of the robust path's own,
+// which the unchanged step reads; the pass's least-squares accumulator still
+// goes to c->model.accum and is not read. After the regroup the permutation
+// and the weights are read again too (point_weights_resident enqueues the
+// regather of stale weights): where the host loop's next evaluation gets them.
 static int descend_lm_device(fsdf_ctx* c, double* x, int32_t iteration_limit, double damping, double max_step,
                              double tolerance, double n_points, double* value_out, int32_t* iterations_out,
                              double* damping_out) {
@@ -464,6 +527,13 @@ static int descend_lm_device(fsdf_ctx* c, double* x, int32_t iteration_limit, do
   if (rc) return rc;
   HIPCHECK(c, c->moments_partials.reserve(fsdf::moments_partials_len(n, S)));
   HIPCHECK(c, c->moments.reserve((size_t)S * fsdf::kMomentsLen));
+  const bool robust = robust_objective(c);
+  if (robust) {
+    HIPCHECK(c, c->robust_partials.reserve(fsdf::robust_partials_len(n, S)));
+    HIPCHECK(c, c->robust_rows.reserve((size_t)S * fsdf::kRobustLen));
+    HIPCHECK(c, c->robust_dev_accum.reserve((size_t)1 + 6 * (size_t)S));
+    HIPCHECK(c, c->robust_dev_moments.reserve((size_t)S * fsdf::kMomentsLen));
+  }
   if (c->solver.capacity() < need) HIPCHECK(c, hipStreamSynchronize(c->stream));  // (an earlier frame's launches)
   HIPCHECK(c, c->solver.reserve(need));
   HIPCHECK(c, c->h_solver.reserve(up + back));
@@ -474,6 +544,19 @@ static int descend_lm_device(fsdf_ctx* c, double* x, int32_t iteration_limit, do
   double* d_partials = c->moments_partials.get();
   double* d_moments = c->moments.get();
   double* d_accum = c->model.accum.get();
+  double* d_d = robust ? c->d.get() : nullptr;
+  double* d_rpartials = c->robust_partials.get();
+  double* d_rows = c->robust_rows.get();
+  // (what the step reads: the robust path's own pair, or the pass's accumulator and the moments kernel's sums)
+  double* d_step_accum = robust ? c->robust_dev_accum.get() : d_accum;
+  double* d_step_moments = robust ? c->robust_dev_moments.get() : d_moments;
+  const int32_t* d_perm = c->cur.perm.get();
+  // (the per-point weights in resident order, regathered when the layout changed since; null: none set)
+  const double* d_conf = nullptr;
+  if (robust) {
+    rc = point_weights_resident(c, &d_conf);
+    if (rc) return rc;
+  }
   double* d = c->solver.get();
   double* h = c->h_solver.get();
   HIPCHECK(c, hipStreamSynchronize(c->stream));  // (the pinned staging of an earlier frame is free)
@@ -498,16 +581,28 @@ static int descend_lm_device(fsdf_ctx* c, double* x, int32_t iteration_limit, do
   HIPCHECK(c, hipMemcpyAsync(d, h, up * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHECK(c, fsdf::launch_solver_init(T, st, c->lm, c->pm, c->precision, c->stream));
   for (int it = 0; it < iteration_limit; ++it) {
-    rc = run_pass(c, nullptr, d_pts, n, d_accum, d_kstar, nullptr, d_grad, nullptr, true, true, ls.flags);
+    rc = run_pass(c, nullptr, d_pts, n, d_accum, d_kstar, d_d, d_grad, nullptr, true, true, ls.flags);
     if (rc) return rc;
-    HIPCHECK(c, fsdf::launch_moments(c->precision, d_pts, d_kstar, d_grad, n, S, d_partials, d_moments, c->stream,
-                                     ls.flags));
-    if (it == 0) {  // (after the moments launch: they read the layout the pass ran on)
+    if (robust) {
+      HIPCHECK(c, fsdf::launch_robust(c->precision, true, d_pts, d_kstar, d_d, d_grad, d_conf, d_perm, c->free_split,
+                                      n, S, c->loss_kind, c->loss_scale, d_rpartials, d_rows, c->stream, ls.flags));
+      HIPCHECK(c, fsdf::launch_robust_assemble(true, d_rows, c->lm.surface_kind, S, d_step_accum, d_step_moments,
+                                               c->stream, ls.flags));
+    } else {
+      HIPCHECK(c, fsdf::launch_moments(c->precision, d_pts, d_kstar, d_grad, n, S, d_partials, d_moments, c->stream,
+                                       ls.flags));
+    }
+    if (it == 0) {  // (after the moments / robust launch: they read the layout the pass ran on)
       rc = iteration_regroup(c);
       if (rc) return rc;
       d_pts = c->cur.pts.get();
+      if (robust) {
+        d_perm = c->cur.perm.get();
+        rc = point_weights_resident(c, &d_conf);
+        if (rc) return rc;
+      }
     }
-    HIPCHECK(c, fsdf::launch_lm_step(T, ls, d_accum, d_moments, it, c->stream));
+    HIPCHECK(c, fsdf::launch_lm_step(T, ls, d_step_accum, d_step_moments, it, c->stream));
     if (it + 1 < iteration_limit)
       HIPCHECK(c, fsdf::launch_lm_pose(T, ls, c->lm, c->pm, c->precision, (it + 1) & 1, c->stream));
   }
@@ -560,14 +655,23 @@ extern "C" int fsdf_descend_lm(fsdf_ctx* c, double* x, int32_t iteration_limit, 
   // points, the moments table and both solver kernels' carves within their LDS
   // A loss other than SQUARE (fsdf_set_loss): the host loop alone (mode 1 takes it, mode 2 is refused).
   // Per-point weights (fsdf_set_point_weights) and a free-space split (fsdf_set_free_split) likewise.
+  // fsdf_set_robust_loops admits them on hull-only rigid scenes whose robust table fits
+  // (descend_lm_device: the robust launch and the assembly feed the step).
   const bool loss = robust_objective(c);
-  if (loss && c->lm_solver_device == 2)
+  // (a non-rigid scene in the required mode was refused above; robust_fit cannot fail under
+  // fsdf_set_surfaces' limit of 256 surfaces, so the refusal below is not reachable today)
+  const bool robust_dev = loss && c->robust_loops && rigid && fsdf::robust_fit(c->lm.S);
+  if (loss && !robust_dev && c->robust_loops && c->lm_solver_device == 2)
+    return fail(c, FSDF_ERR_STATE,
+                "descend_lm: the device loop was required (fsdf_set_lm_solver 2) under a robust objective "
+                "(fsdf_set_robust_loops) but the scene has more surfaces than the robust table's LDS holds (at most 282)");
+  if (loss && !robust_dev && c->lm_solver_device == 2)
     return fail(c, FSDF_ERR_STATE, "descend_lm: the device loop was required (fsdf_set_lm_solver 2) but %s "
                                    "(loss kind %d: the host loop serves it)",
                 c->free_split >= 0 ? "a free-space split is set (fsdf_set_free_split)" :
                 c->conf_set ? "per-point weights are set (fsdf_set_point_weights)" : "a loss is set (fsdf_set_loss)",
                 c->loss_kind);
-  if (rigid && c->lm_solver_device && iteration_limit > 0 && !loss) {
+  if (rigid && c->lm_solver_device && iteration_limit > 0 && (!loss || robust_dev)) {
     const bool required = c->lm_solver_device == 2;
     if (required && !(damping > 0.0))
       return fail(c, FSDF_ERR_ARG, "descend_lm: the device loop needs a damping > 0");

@@ -299,10 +299,22 @@ size_t robust_partials_len(int64_t n, int S);
 // free-space sample iff (d_perm ? d_perm[i] : i) >= n_surface (d_perm: null, or
 // the cloud's resident→caller permutation [n]) and then counts only where
 // d* < 0 (robust_impl.h one_sided_factor); n_surface < 0: no split, d_perm unread.
+// skip (optional): a device flag, as launch_moments'; set, both launches return
+// at once (the evaluations a finished device frame still has queued). It is
+// written only by a step kernel launched earlier on the same stream.
 hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
                          const double* d_grad, const double* d_conf, const int32_t* d_perm, int64_t n_surface,
                          int64_t n, int S, int kind, double scale, double* d_partials, double* d_rows,
-                         hipStream_t s);
+                         hipStream_t s, const int* skip = nullptr);
+// robust_rows_finish (pass.hip) on the device: from d_rows [S][29] (moments) or
+// [S][8] the accumulator d_accum [1 + 6S] — [0] Σρ summed over the surfaces in
+// ascending order from 0.0 by one thread, then every hull surface's wrench, 0.0
+// for a surface that is no hull — and, moments, d_moments [S][21] (a hull's row
+// copied, any other's 0.0): the host's bits. d_surface_kind [S]: the model's
+// (LocalModel::surface_kind). Any S >= 1; one launch; skip as launch_robust's.
+constexpr int kRobustAssembleBlock = 128;  // (two tiles of Σρ at the library's 256 surfaces)
+hipError_t launch_robust_assemble(bool moments, const double* d_rows, const int32_t* d_surface_kind, int S,
+                                  double* d_accum, double* d_moments, hipStream_t s, const int* skip = nullptr);
 // ---- the RBF skins' blocks under a robust objective (robust_skin.hip) -----------
 // d_blocks [lm.rbf_acc]: per skin r its block of the accumulator, Σ t j(p) over
 // the resident points with k* = r's surface — rbf_adjoint's sums with the

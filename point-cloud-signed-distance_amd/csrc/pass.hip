@@ -653,6 +653,71 @@ extern "C" int fsdf_eval_robust(fsdf_ctx* c, const double* poses, double* cost_o
   return FSDF_OK;
 }
 
+// fsdf_eval_robust without its synchronisation and read-back: the pass, the
+// robust launch and the rows' assembly on the device (robust.hip
+// robust_assemble_kernel: robust_rows_finish's arithmetic) into the caller's
+// device buffers, all in order on the context stream. The order is
+// run_pass_robust's: reserve, read the pointers, launch. A cloud of no points
+// launches no robust kernel: zeros.
+extern "C" int fsdf_eval_robust_device(fsdf_ctx* c, const double* poses, double* d_accum, double* d_moments) {
+  if (!c) return FSDF_ERR_ARG;
+  if (c->lm.S == 0) return fail(c, FSDF_ERR_STATE, "eval_robust_device: no model (call fsdf_set_model first)");
+  if (!poses || !d_accum) return fail(c, FSDF_ERR_ARG, "eval_robust_device: poses and d_accum are required");
+  HIPCHECK(c, hipSetDevice(c->device));
+  if (c->lm.R > 0 || c->mech.n_deform > 0)
+    return fail(c, FSDF_ERR_STATE, "eval_robust_device: hull-only scenes (the scene has an RBF skin or a deformation)%s",
+                c->free_split >= 0 ? "; a free-space split is set (fsdf_set_free_split)" : "");
+  const int S = c->lm.S;
+  if (!fsdf::robust_fit(S))
+    return fail(c, FSDF_ERR_STATE,
+                "eval_robust_device: the robust table of %d surfaces (%zu bytes) does not fit %d bytes of LDS (at most "
+                "282 surfaces)", S, (size_t)S * fsdf::kRobustLen * sizeof(double), fsdf::kRobustMaxLds);
+  const bool moments = d_moments != nullptr;
+  const int64_t n = c->n;
+  // (1) reserve
+  int rc = ensure_outputs(c, n);
+  if (rc) return rc;
+  HIPCHECK(c, c->robust_partials.reserve(fsdf::robust_partials_len(n, S)));
+  HIPCHECK(c, c->robust_rows.reserve((size_t)S * fsdf::kRobustLen));
+  // (2) read the pointers
+  const void* d_pts = c->cur.pts.get();
+  int32_t* d_kstar = c->kstar.get();
+  double* d_d = c->d.get();
+  double* d_grad = c->grad.get();
+  double* d_partials = c->robust_partials.get();
+  double* d_rows = c->robust_rows.get();
+  double* d_ls = c->model.accum.get();  // (the pass's own least-squares accumulator: not read)
+  const double* d_conf = nullptr;
+  rc = point_weights_resident(c, &d_conf);
+  if (rc) return rc;
+  // (3) launch
+  rc = run_pass(c, poses, d_pts, n, d_ls, d_kstar, d_d, d_grad, nullptr, true);
+  if (rc) return rc;
+  if (n == 0) {
+    HIPCHECK(c, hipMemsetAsync(d_accum, 0, ((size_t)1 + 6 * (size_t)S) * sizeof(double), c->stream));
+    if (moments) HIPCHECK(c, hipMemsetAsync(d_moments, 0, (size_t)S * fsdf::kMomentsLen * sizeof(double), c->stream));
+    return FSDF_OK;
+  }
+  HIPCHECK(c, fsdf::launch_robust(c->precision, moments, d_pts, d_kstar, d_d, d_grad, d_conf, c->cur.perm.get(),
+                                  c->free_split, n, S, c->loss_kind, c->loss_scale, d_partials, d_rows, c->stream));
+  HIPCHECK(c, fsdf::launch_robust_assemble(moments, d_rows, c->lm.surface_kind, S, d_accum, d_moments, c->stream));
+  return FSDF_OK;
+}
+
+// ---- the device solver loops on a robust objective (descend.hip) --------------------------
+extern "C" int fsdf_set_robust_loops(fsdf_ctx* c, int32_t enable) {
+  if (!c) return FSDF_ERR_ARG;
+  if (enable != 0 && enable != 1) return fail(c, FSDF_ERR_ARG, "set_robust_loops: enable %d", enable);
+  c->robust_loops = enable;
+  return FSDF_OK;
+}
+
+extern "C" int fsdf_get_robust_loops(const fsdf_ctx* c, int32_t* enable_out) {
+  if (!c || !enable_out) return FSDF_ERR_ARG;
+  *enable_out = c->robust_loops;
+  return FSDF_OK;
+}
+
 // ---- robust objectives on RBF skins and deformations (robust_skin.hip) --------------------
 extern "C" int fsdf_set_robust_skins(fsdf_ctx* c, int32_t enable) {
   if (!c) return FSDF_ERR_ARG;

@@ -37,6 +37,12 @@
 // by 0.0 for a sample outside the model and the WEIGHTED arithmetic follows, so
 // the bits are those of the weighted kernel given weights a · gate; table, run
 // and wave layout are unchanged.
+//
+// skip (the device solver loops, fsdf_set_robust_loops): a device flag a frame's
+// step kernel raises when the frame is done; robust_kernel, the tile reduce and
+// robust_assemble_kernel — the rows into the accumulator [1 + 6S] and the
+// moments [S][21] the step kernels read, robust_rows_finish's arithmetic on the
+// device — then return at once. skip == nullptr is the launch without it.
 
 #include <hip/hip_runtime.h>
 
@@ -87,7 +93,12 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
                                                               int run, int kind, double scale,
                                                               double* __restrict__ partials,
                                                               const double* __restrict__ conf,
-                                                              const int32_t* __restrict__ perm, int64_t n_surface) {
+                                                              const int32_t* __restrict__ perm, int64_t n_surface,
+                                                              const int* __restrict__ skip) {
+  // (uniform: a finished device frame — one address for every thread of the launch, written only by
+  // a step kernel of an earlier launch on the same stream, so every wave of every workgroup reads
+  // the same value and leaves, or stays, as a whole: no barrier below is reached by a part of one)
+  if (skip && *skip) return;
   constexpr int LEN = MOMENTS ? kRobustLen : kRobustTail;
   constexpr bool FACTOR = WEIGHTED || ONE_SIDED;  // a point's terms carry a factor a
   constexpr int M0 = LEN - kRobustTail;  // the wrench's first entry; Σρ at M0 + 6, Σw at M0 + 7
@@ -178,7 +189,7 @@ __global__ __launch_bounds__(kRobustBlock) void robust_kernel(const T* __restric
 hipError_t launch_robust(int precision, bool moments, const void* d_pts, const int32_t* d_kstar, const double* d_d,
                          const double* d_grad, const double* d_conf, const int32_t* d_perm, int64_t n_surface,
                          int64_t n, int S, int kind, double scale, double* d_partials, double* d_rows,
-                         hipStream_t s) {
+                         hipStream_t s, const int* skip) {
   if (n <= 0 || !robust_fit(S) || !robust::valid(kind, scale) || !d_pts || !d_kstar || !d_d || !d_grad ||
       !d_partials || !d_rows)
     return hipErrorInvalidValue;
@@ -187,7 +198,7 @@ hipError_t launch_robust(int precision, bool moments, const void* d_pts, const i
   const size_t lds = (size_t)waves * S * len * sizeof(double);
 #define FSDF_ROBUST_LAUNCH(T, M, W, O)                                                                         \
   hipLaunchKernelGGL((robust_kernel<T, M, W, O>), dim3(groups), dim3(block), lds, s, (const T*)d_pts, d_kstar, \
-                     d_d, d_grad, n, S, run, kind, scale, d_partials, d_conf, d_perm, n_surface)
+                     d_d, d_grad, n, S, run, kind, scale, d_partials, d_conf, d_perm, n_surface, skip)
 #define FSDF_ROBUST_LAUNCH_M(T, W, O)              \
   do {                                             \
     if (moments) FSDF_ROBUST_LAUNCH(T, true, W, O); \
@@ -213,7 +224,73 @@ hipError_t launch_robust(int precision, bool moments, const void* d_pts, const i
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // the partials in workgroup order (the pass's tile reduce: fixed order)
-  return launch_reduce(d_partials, groups, len * S, d_rows, s);
+  return launch_reduce(d_partials, groups, len * S, d_rows, s, nullptr, nullptr, nullptr, skip);
+}
+
+// The accumulator in fsdf_eval's layout and — MOMENTS — the [S][21] moments from
+// the reduced rows, on the device: robust_rows_finish's (pass.hip) arithmetic.
+// One thread per entry copied — surface k's 6 wrench entries to accum[1 + 6k ..],
+// its 21 moments to moments[21k ..]; a surface that is no hull gets 0.0 in their
+// place — over as many workgroups as the S · (6 [+ 21]) entries need, so any S
+// is served. accum[0] = Σρ is summed by thread 0 of workgroup 0 alone, serially
+// over the surfaces in ascending order from 0.0: the host's order is what the
+// bits are (at most 256 additions: the library's surface limit; tiles of
+// kRobustAssembleBlock serve any S).
+template <bool MOMENTS>
+__global__ __launch_bounds__(kRobustAssembleBlock) void robust_assemble_kernel(const double* __restrict__ rows,
+                                                                               const int32_t* __restrict__ surface_kind,
+                                                                               int S, double* __restrict__ accum,
+                                                                               double* __restrict__ moments,
+                                                                               const int* __restrict__ skip) {
+  // (uniform: a finished device frame; the flag is written only by a step kernel of an earlier
+  // launch on the same stream, as robust_kernel's)
+  if (skip && *skip) return;
+  constexpr int LEN = MOMENTS ? kRobustLen : kRobustTail;
+  constexpr int M0 = LEN - kRobustTail;  // the wrench's first entry; Σρ at M0 + 6
+  constexpr int PER = 6 + (MOMENTS ? kMomentsLen : 0);  // entries copied per surface
+  const int t = blockIdx.x * kRobustAssembleBlock + threadIdx.x;
+  if (t < S * PER) {
+    const int k = t / PER, e = t - k * PER;
+    const bool hull = surface_kind[k] == 0;  // (FSDF_SURFACE_HULL)
+    const double* r = rows + (size_t)LEN * k;
+    if (e < 6)
+      accum[1 + 6 * k + e] = hull ? r[M0 + e] : 0.0;
+    else if (MOMENTS)
+      moments[kMomentsLen * k + (e - 6)] = hull ? r[e - 6] : 0.0;
+  }
+  // Σρ, workgroup 0 (block-uniform: its barriers are reached by the whole workgroup): the
+  // surfaces' Σρ come into LDS a tile of one per thread at a time — the loads side by side, not
+  // one round trip to memory per surface (13 µs at S = 64 that way) — and thread 0 adds each
+  // tile serially: ascending k from 0.0, the host's order
+  if (blockIdx.x == 0) {
+    __shared__ double rho[kRobustAssembleBlock];
+    double cost = 0.0;
+    for (int base = 0; base < S; base += kRobustAssembleBlock) {
+      const int k = base + (int)threadIdx.x;
+      if (k < S) rho[threadIdx.x] = rows[(size_t)LEN * k + M0 + 6];
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const int m = S - base < kRobustAssembleBlock ? S - base : kRobustAssembleBlock;
+        for (int j = 0; j < m; ++j) cost += rho[j];
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) accum[0] = cost;
+  }
+}
+
+hipError_t launch_robust_assemble(bool moments, const double* d_rows, const int32_t* d_surface_kind, int S,
+                                  double* d_accum, double* d_moments, hipStream_t s, const int* skip) {
+  if (S < 1 || !d_rows || !d_surface_kind || !d_accum || (moments && !d_moments)) return hipErrorInvalidValue;
+  const int per = 6 + (moments ? kMomentsLen : 0);
+  const int groups = (S * per + kRobustAssembleBlock - 1) / kRobustAssembleBlock;
+  if (moments)
+    hipLaunchKernelGGL(robust_assemble_kernel<true>, dim3(groups), dim3(kRobustAssembleBlock), 0, s, d_rows,
+                       d_surface_kind, S, d_accum, d_moments, skip);
+  else
+    hipLaunchKernelGGL(robust_assemble_kernel<false>, dim3(groups), dim3(kRobustAssembleBlock), 0, s, d_rows,
+                       d_surface_kind, S, d_accum, d_moments, skip);
+  return hipGetLastError();
 }
 
 }  // namespace fsdf

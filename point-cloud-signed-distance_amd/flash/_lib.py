@@ -151,6 +151,9 @@ _PROTOS = {
     "fsdf_get_robust_skins": (c_int32, [c_void_p, POINTER(c_int32)]),
     "fsdf_eval_robust_skins": (c_int32, [c_void_p, c_void_p, POINTER(c_double), c_void_p, c_void_p, c_void_p,
                                          c_void_p]),
+    "fsdf_set_robust_loops": (c_int32, [c_void_p, c_int32]),
+    "fsdf_get_robust_loops": (c_int32, [c_void_p, POINTER(c_int32)]),
+    "fsdf_eval_robust_device": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fsdf_score_poses": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "fsdf_score_states": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "fsdf_score_time": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
@@ -830,6 +833,33 @@ class Context:
             off = np.concatenate([[0], np.cumsum([m * m for m in ms])]).astype(int)
             skin_mom = [flat[off[i]: off[i + 1]].reshape(m, m) for i, m in enumerate(ms)]
         return cost.value, accum, mom, skin_mom, wts
+
+    def set_robust_loops(self, enable: bool):
+        """fsdf_set_robust_loops: a robust objective (a loss, point weights, a
+        free split) may run on the device-resident solver loops — descend under
+        set_solver(True / "require") and descend_lm under set_lm_solver(True /
+        "require") — on hull-only rigid scenes; bit-identical to the host loop.
+        Off by default: such objectives then take the host loop and the required
+        modes are refused, as before. Scenes with RBF skins or deformations keep
+        the host loop either way. A context setting."""
+        check(self._lib.fsdf_set_robust_loops(self._ctx, int(bool(enable))), self._ctx, "set_robust_loops")
+        self.robust_loops = bool(enable)
+
+    def get_robust_loops(self) -> bool:
+        """fsdf_get_robust_loops: the switch as the library holds it."""
+        v = c_int32(0)
+        check(self._lib.fsdf_get_robust_loops(self._ctx, ctypes.byref(v)), self._ctx, "get_robust_loops")
+        return bool(v.value)
+
+    def eval_robust_device(self, poses, d_accum: int, d_moments: int = 0):
+        """fsdf_eval_robust_device: eval_robust without the synchronisation and
+        the read-back — the pass, the robust launch and the rows' assembly
+        enqueued, writing accum [1 + 6K] and (d_moments nonzero) moments
+        [K, 21] into device buffers (raw device pointers, fp64): eval_robust's
+        accum and moments bit for bit once the stream reaches them."""
+        p = self._poses(poses)
+        check(self._lib.fsdf_eval_robust_device(self._ctx, ptr(p), c_void_p(d_accum), c_void_p(d_moments or 0)),
+              self._ctx, "eval_robust_device")
 
     def eval_device(self, poses, d_accum: int, d_kstar: int = 0, d_d: int = 0, d_grad: int = 0):
         """Asynchronous pass writing into device buffers (raw device pointers)."""

@@ -130,9 +130,13 @@ class CostFunctor:
     — what the solvers divide the cost by — is their sum, the input cloud's
     size; under "unit" it is `n_points`."""
 
+    # (the switch's default lives on the class: a functor assembled without __init__ — the stand-ins
+    # of tests/test_robust_skins.py — has it off, and _assert_loss reads it plainly)
+    robust_loops = False
+
     def __init__(self, manipulator: Manipulator, sensed_points, device: int = 0, precision: int = 64,
                  deformation_cost_weight=default_deformation_cost_weight, skin_hessian: bool = False, loss=None,
-                 robust_skins: bool = False, voxel=None):
+                 robust_skins: bool = False, voxel=None, robust_loops: bool = False):
         self.manipulator = manipulator
         self.voxel = voxel
         self.weight = deformation_cost_weight
@@ -164,6 +168,12 @@ class CostFunctor:
         self.robust_skins = False
         if robust_skins:
             self.set_robust_skins(True)
+        # robust_loops: a loss, point weights and a free split may run on the
+        # device-resident solver loops of descend / descend_lm (fsdf_set_robust_loops;
+        # rigid scenes — where the loop runs stays set_solver's / device_loop's say)
+        self.robust_loops = False
+        if robust_loops:
+            self.set_robust_loops(True)
         # loss: a robust point loss (flash.robust.Huber / Tukey; None: least
         # squares) for __call__, value_and_gradient, value_gradient_hessian,
         # descend and descend_lm (fsdf_set_loss; native rigid scenes, others
@@ -323,12 +333,30 @@ class CostFunctor:
         if self._native:
             self.ctx.set_robust_skins(self.robust_skins)
 
+    def set_robust_loops(self, enable: bool = True):
+        """Let the robust objective (set_loss, set_point_weights,
+        set_free_split, a DepthFrame's free_space, a VoxelGrid's counts) run on
+        the device-resident loops of descend and descend_lm
+        (fsdf_set_robust_loops): rigid native scenes, bit-identical to the host
+        loop. Off (the default), such an objective takes the host loop and
+        device_loop="require" / set_solver("require") are refused. Where the
+        loop runs is still LevenbergMarquardt(device_loop=…)'s and
+        Context.set_solver's say; scenes with RBF skins or deformations keep
+        the host loop."""
+        if enable and not self._native:
+            raise NotImplementedError("robust_loops: scene is not native-capable")
+        self.robust_loops = bool(enable)
+        if self._native:
+            self.ctx.set_robust_loops(self.robust_loops)
+
     def _assert_loss(self):
         # (the engine is shared: another functor of it may have set its own)
         if self.ctx.loss != self.loss:
             self.ctx.set_loss(self.loss)
         if self._native and getattr(self.ctx, "robust_skins", False) != self.robust_skins:
             self.ctx.set_robust_skins(self.robust_skins)
+        if self._native and getattr(self.ctx, "robust_loops", False) != self.robust_loops:
+            self.ctx.set_robust_loops(self.robust_loops)
 
     def set_skin_hessian(self, enable: bool = True):
         """Turn the Gauss-Newton Hessian of non-rigid scenes on or off

@@ -206,6 +206,11 @@ def _frame_weights(weights, points):
     return np.asarray(weights, np.float64).reshape(-1)
 
 
+def _loops_kw(robust_loops):
+    # (handed to the functor only when asked for: a functor without the switch is built as before)
+    return {"robust_loops": True} if robust_loops else {}
+
+
 def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, loss=None, weights=None,
               robust_skins: bool = False):
     """wrapped_cost (src/tracking.jl:16-21) over a CostFunctor, then optimize!.
@@ -219,8 +224,9 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, l
     loss (flash.robust.Huber / Tukey; None: the functor as it is): handed to
     the functor (CostFunctor.set_loss) before anything runs, so every path
     above — the native loops, the Python loops, the callback's cost — is over
-    the robust objective Σρ(d*)/N. The device-resident loops do not serve a
-    loss: device_loop=True runs the host loop, "require" is refused.
+    the robust objective Σρ(d*)/N. The device-resident loops serve a loss
+    only in a functor with robust_loops on (CostFunctor.set_robust_loops);
+    otherwise device_loop=True runs the host loop and "require" is refused.
     weights (one confidence weight per point of the functor's cloud; None: the
     functor as it is): handed to the functor (CostFunctor.set_point_weights)
     before anything runs, under the loss's rules. n_points stays the divisor:
@@ -284,7 +290,7 @@ def _optimize(cost: CostFunctor, n_points: int, x_estimated, callback, solver, l
 
 def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callback=None, solver=None,
                    device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False,
-                   voxel=None):
+                   voxel=None, robust_loops: bool = False):
     """Tracking.estimate_state (src/tracking.jl:8-27). Returns the solution x.
 
     The default callback accepts (x, c): the reference's default `x -> ()` is
@@ -297,6 +303,11 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
     after the cloud is resident.
     robust_skins: loss, weights and a frame's free space also serve native
     scenes with RBF skins and deformations (fsdf_set_robust_skins).
+    robust_loops: a loss, weights, a frame's free space and a grid's counts may
+    run on the device-resident solver loops (fsdf_set_robust_loops; native rigid
+    scenes, the same bits as the host loop). Where the loop runs is still the
+    solver's say (LevenbergMarquardt(device_loop=…), Context.set_solver); off,
+    such an objective takes the host loop and device_loop="require" is refused.
     sensed_points may be a depthsensors.DepthFrame (the depth image, the
     sensor and its pose): the device forms the cloud (fsdf_set_depth_*), N is
     the number of valid pixels, and the host forms the points only for a
@@ -321,12 +332,14 @@ def estimate_state(manipulator: Manipulator, sensed_points, x_estimated, callbac
         if not isinstance(sensed_points, DepthFrame):
             sensed_points = np.asarray(sensed_points, np.float64).reshape(-1, 3)
         kw = {} if voxel is None else {"voxel": voxel}
+        kw.update(_loops_kw(robust_loops))
         cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision,
                            robust_skins=robust_skins, **kw)
         pts = lambda: cost.sensed_points  # noqa: E731 (formed when asked for)
     else:
         pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
-        cost = CostFunctor(manipulator, pts, device=device, precision=precision, robust_skins=robust_skins)
+        cost = CostFunctor(manipulator, pts, device=device, precision=precision, robust_skins=robust_skins,
+                           **_loops_kw(robust_loops))
     return _optimize(cost, getattr(cost, "n_divisor", cost.n_points), x_estimated, callback, solver, loss=loss,
                      weights=_frame_weights(weights, pts), robust_skins=robust_skins)
 
@@ -398,7 +411,8 @@ def _multi_start_on(cost, n_points: int, candidates, keep, solver, callback):
 
 
 def multi_start(manipulator: Manipulator, sensed_points, candidates, keep: int = 1, solver=None, loss=None,
-                weights=None, voxel=None, device: int = 0, precision: int = 64, callback=None):
+                weights=None, voxel=None, device: int = 0, precision: int = 64, callback=None,
+                robust_loops: bool = False):
     """A start in the right basin, found rather than given: score every
     candidate state against the cloud in one batch of launches
     (CostFunctor.score, fsdf_score_states), keep the `keep` lowest, refine each
@@ -413,7 +427,7 @@ def multi_start(manipulator: Manipulator, sensed_points, candidates, keep: int =
     Selection rule (select_candidates): NaN ranks last, equal values by lower
     index — for the scores and for the refined costs (in `kept` order) alike.
     sensed_points, loss, weights, voxel, device, precision, callback and solver
-    are estimate_state's (a DepthFrame and a VoxelGrid included); candidates is
+    and robust_loops are estimate_state's (a DepthFrame and a VoxelGrid included); candidates is
     [B, n_states] (candidates_around draws them). Native rigid scenes."""
     solver = solver or _default_solver(manipulator)
     X = np.ascontiguousarray(candidates, np.float64)
@@ -425,11 +439,12 @@ def multi_start(manipulator: Manipulator, sensed_points, candidates, keep: int =
         if not isinstance(sensed_points, DepthFrame):
             sensed_points = np.asarray(sensed_points, np.float64).reshape(-1, 3)
         kw = {} if voxel is None else {"voxel": voxel}
+        kw.update(_loops_kw(robust_loops))
         cost = CostFunctor(manipulator, sensed_points, device=device, precision=precision, **kw)
         pts = lambda: cost.sensed_points  # noqa: E731 (formed when asked for)
     else:
         pts = np.asarray(sensed_points, np.float64).reshape(-1, 3)
-        cost = CostFunctor(manipulator, pts, device=device, precision=precision)
+        cost = CostFunctor(manipulator, pts, device=device, precision=precision, **_loops_kw(robust_loops))
     # (the objective the candidates are scored under is the one they are refined under)
     if loss is not None:
         cost.set_loss(loss)
@@ -453,12 +468,15 @@ class Tracker:
 
     def __init__(self, manipulator: Manipulator, state: ManipulatorState | None = None, solver=None,
                  device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False,
-                 voxel=None):
+                 voxel=None, robust_loops: bool = False):
         self.manipulator = manipulator
         self.state = state if state is not None else ManipulatorState(manipulator)
         self.solver = solver or notebook_frame_solver(manipulator)
         self.cost = CostFunctor(manipulator, np.zeros((0, 3)), device=device, precision=precision,
-                                robust_skins=robust_skins)
+                                robust_skins=robust_skins, **_loops_kw(robust_loops))
+        # a robust objective may run on the device-resident loops (step and relocalize alike: the
+        # functor carries the switch)
+        self.robust_loops = bool(robust_loops)
         self.robust_skins = bool(robust_skins)  # loss / weights / free space also on skins and deformations
         self.loss = loss  # a robust point loss for every frame (flash.robust; None: least squares)
         # per-point confidence weights: a callable points -> weights applied to every frame (an
@@ -549,7 +567,8 @@ class Tracker:
 
 
 def track(manipulator: Manipulator, frames, state: ManipulatorState | None = None, solver=None, callback=None,
-          device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False, voxel=None):
+          device: int = 0, precision: int = 64, loss=None, weights=None, robust_skins: bool = False, voxel=None,
+          robust_loops: bool = False):
     """for event in log: gradient_descent!(state, model, sensed_points)
     (examples/irb_and_squishable.ipynb cells 11-12). `frames` yields sensed
     clouds ([n,3]) or depthsensors.DepthFrames (made resident by the device
@@ -559,13 +578,13 @@ def track(manipulator: Manipulator, frames, state: ManipulatorState | None = Non
     loss: a robust point loss for every frame (flash.robust).
     weights: a callable points -> weights applied to every frame (or one array,
     where every frame has as many points).
-    robust_skins: as estimate_state's.
+    robust_skins, robust_loops: as estimate_state's.
     voxel: a depthdata.VoxelGrid every frame is thinned through (as
     estimate_state's). With it set the next cloud is NOT prefetched — the grid
     stage has no prefetched form —, so a frame's upload does not overlap the
     previous frame's iterations."""
     tr = Tracker(manipulator, state, solver, device, precision, loss=loss, weights=weights,
-                 robust_skins=robust_skins, voxel=voxel)
+                 robust_skins=robust_skins, voxel=voxel, robust_loops=robust_loops)
     xs = []
     it = iter(frames)
     cur = next(it, None)

@@ -20,7 +20,9 @@ scaled per coordinate by the points of the joint's subtree (--prior-scale
 subtree: W · N / points nearest a surface of the subtree; f is then the wrapped
 objective's, the prior included). --loss huber:0.02 | tukey:0.05 gives every
 frame (and, without --frames, every timed call) that robust point loss
-(fsdf_set_loss: f is then Σρ/N, the LM frames run the host loop); the table
+(fsdf_set_loss: f is then Σρ/N, the LM frames run the host loop — with
+--robust-loops the functor turns fsdf_set_robust_loops on, and --device-loop
+then runs them, and the NaiveSolver frames, on the device-resident loops); the table
 also carries the error over the three base joints of each arm. --weights
 depth | random gives the resident cloud per-point confidence weights
 (fsdf_set_point_weights; set again after every cloud swap): depth the axial
@@ -113,7 +115,7 @@ def frames(a):
         q_true, q = synthetic.perturbed_configuration(m, 1234)
         q = np.asarray(q, np.float64)
         pts = synthetic.depth_cloud(m, q_true, n, seed=1234 + 17)
-        cf = CostFunctor(m, pts, loss=a.loss)
+        cf = CostFunctor(m, pts, loss=a.loss, **({"robust_loops": True} if a.robust_loops else {}))
         w = point_weights(a.weights, pts)
         f_true = cf.value_and_gradient(np.asarray(q_true, np.float64))[0] / n
         # the three base joints of each arm (IRB140: six revolute joints per arm, in arm order)
@@ -146,7 +148,8 @@ def frames(a):
                        "prior_scale": a.prior_scale if a.prior is not None else None,
                        "max_abs_q_error": float(np.abs(x - q_true).max()),
                        "max_abs_base_joint_error": float(np.abs(x - q_true)[base].max()),
-                       "loss": repr(a.loss) if a.loss is not None else None, "weights": a.weights}
+                       "loss": repr(a.loss) if a.loss is not None else None, "weights": a.weights,
+                       "robust_loops": bool(a.robust_loops)}
                 print(json.dumps(out), flush=True)
                 if a.json:
                     with open(a.json, "a") as fh:
@@ -209,6 +212,8 @@ if __name__ == "__main__":
     p.add_argument("--loss", default=None, help="huber:SCALE or tukey:SCALE (flash.robust.parse)")
     p.add_argument("--weights", choices=["depth", "random"], default=None,
                    help="per-point confidence weights for the resident cloud (fsdf_set_point_weights)")
+    p.add_argument("--robust-loops", action="store_true",
+                   help="a robust objective may run on the device-resident loops (fsdf_set_robust_loops)")
     a = p.parse_args()
     if a.loss is not None:
         from flash import robust
