@@ -67,10 +67,10 @@ def fold_configuration(mechanism, x):
 
 def fk_ref(mechanism, x):
     """(R [.., nb, 3, 3], t [.., nb, 3], Rb, tb) of every body and joint frame
-    at x [.., nx] — float64, complex128 or np.longdouble, batched over leading
-    axes. numpy's own sin and cos."""
+    at x [.., nx] — float64, complex128, np.longdouble or np.clongdouble,
+    batched over leading axes. numpy's own sin and cos."""
     x = np.asarray(x)
-    dt = x.dtype if x.dtype in (np.complex128, np.longdouble) else np.float64
+    dt = x.dtype if x.dtype in (np.complex128, np.longdouble, np.clongdouble) else np.float64
     x = x.astype(dt)
     tree = _tree(mechanism)
     nb, lead = len(tree), x.shape[:-1]
