@@ -970,6 +970,98 @@ int fsdf_score_poses(fsdf_ctx* ctx, const double* poses /* [B][S][12] */, int32_
 int fsdf_score_states(fsdf_ctx* ctx, const double* x /* [B][nq] */, int32_t B, double* cost_out /* [B] */);
 int fsdf_score_time(fsdf_ctx* ctx, double* total_ms_out, int64_t* launches_out);
 
+/* ---- gradients of candidate states ------------------------------------------------
+ * The scoring calls above rank B candidates; refining the kept ones is one
+ * solver loop after the other, every evaluation of every candidate a pose
+ * launch, a pass, a robust launch, a reduce, a read-back and a synchronisation
+ * — on the thinned clouds multi-start runs on, nearly all fixed cost. These
+ * calls give (f, g, H) at B states of the resident cloud at once, and run the
+ * two solver loops over a batch in lockstep with one synchronisation per round
+ * for the whole batch (csrc/batch.hip, csrc/batch_api.hip).
+ *
+ * Per candidate b the device forms the rows fsdf_eval_robust reduces at b's
+ * poses — per surface the 21 moments, the wrench, Σρ and Σw (or the last 8
+ * alone when no moments are asked for) — under the context's loss
+ * (FSDF_LOSS_SQUARE too), per-point weights and free-space split, over the
+ * resident cloud in resident order: one pose launch over (item x candidate)
+ * into the scoring calls' posed tables, one evaluation launch over (chunk group
+ * x candidate) that writes k*, d* and ∇d* per (candidate, point) — 36 bytes —
+ * into a slice buffer, then fsdf_eval_robust's own reduction, statement for
+ * statement, with the candidate on the grid's second dimension. A large batch
+ * runs in slices of a fixed byte budget (tables, per-point blocks, partials,
+ * rows; the environment variable FSDF_BATCH_SLICE_BYTES overrides it; at least
+ * one candidate a slice). Candidate b's rows are bit-identical to the rows
+ * fsdf_eval_robust returns at the same poses on the same cloud layout, and
+ * depend neither on B, nor on b's place in the batch, nor on the slicing. No
+ * floating-point atomics.
+ *
+ * fsdf_batch_robust_poses: poses [B][S][12] -> accum_out [B][1 + 6S], the
+ * accumulator of fsdf_eval_robust per candidate ([0] Σρ summed over the
+ * surfaces in ascending order from 0.0, then the wrenches); moments_out
+ * [B][S][21] and weight_out [B][S] (Σw per surface) may be NULL.
+ *
+ * fsdf_batch_states: x [B][nq] after fsdf_set_mechanism -> cost_out [B],
+ * grad_out [B][nq], hess_out [B][nq][nq] (may be NULL). Per candidate the host
+ * forward kinematics of fsdf_score_states, then on its accumulator and moments
+ * the chain rule and the Gauss-Newton matrix (factor 2) of
+ * fsdf_value_and_gradient / fsdf_value_gradient_hessian under a robust
+ * objective — the same (c, g, H) bits as those calls at x on the same layout
+ * (they may regroup the cloud: compare with FSDF_REGROUP_OFF). hess_out NULL
+ * reduces the rows of 8 and gives the same (c, g) bits.
+ *
+ * fsdf_descend_lm_batch: fsdf_lm_minimize's loop for B candidates in lockstep
+ * over fsdf_descend_lm's objective — cost / n_points and the prior of
+ * fsdf_set_lm_prior about each candidate's own start x[b] —, one
+ * fsdf_batch_states per round over the candidates still running, in ascending
+ * index order. x [B][nq] is updated in place; value_out [B], iterations_out [B]
+ * (evaluations made) and damping_out [B] as fsdf_lm_minimize's, per candidate,
+ * and bit-identical to it over fsdf_batch_states of a single state.
+ * fsdf_descend_batch: the same for the NaiveSolver rule of fsdf_descend's host
+ * loop (divisors [nq] or NULL, shared by the candidates). fsdf_set_solver,
+ * fsdf_set_lm_solver and fsdf_set_robust_loops do not apply: both are host
+ * loops around a batched device evaluation.
+ *
+ * All are synchronous and read-only on the context, as the scoring calls:
+ * seeds, plan, block orders, regroup state, loss, weights, split and the
+ * record of prepared states stay as they are. B = 0 is FSDF_OK and writes
+ * nothing; a cloud of no points gives exact zeros; a candidate with a
+ * non-finite pose entry gets NaN outputs — on a cloud of no points too — and
+ * the others theirs (in the loops
+ * it runs on as under a callback that returns those NaNs). NULL arguments and
+ * B < 0 are FSDF_ERR_ARG. FSDF_ERR_STATE: no model, no cloud, no mechanism
+ * (all but fsdf_batch_robust_poses), a scene with an RBF skin or a
+ * deformation, a ranged or keyed cloud, a prefetched cloud not yet made
+ * resident, more surfaces than the robust table holds. A configuration the
+ * kinematics refuses fails the call.
+ *
+ * fsdf_descend_lm_batch_ref / fsdf_descend_batch_ref: the two loops with every
+ * floating-point scalar read through a pointer, for bindings that pass them by
+ * reference (julia/FlashSDF.jl), as fsdf_set_loss_ref: params [4] = (damping,
+ * max_step, tolerance, n_points), respectively (rate, max_step, tolerance,
+ * n_points); NULL params is FSDF_ERR_ARG; everything else as the call it names.
+ *
+ * fsdf_batch_time: as fsdf_score_time, for the device work of these calls, with
+ * a pair of events around every slice's launches: launches_out counts the
+ * slices run (one per call unless the byte budget split its batch). */
+int fsdf_batch_robust_poses(fsdf_ctx* ctx, const double* poses /* [B][S][12] */, int32_t B,
+                            double* accum_out /* [B][1+6S] */, double* moments_out /* [B][S][21] or NULL */,
+                            double* weight_out /* [B][S] or NULL */);
+int fsdf_batch_states(fsdf_ctx* ctx, const double* x /* [B][nq] */, int32_t B, double* cost_out /* [B] */,
+                      double* grad_out /* [B][nq] */, double* hess_out /* [B][nq][nq] or NULL */);
+int fsdf_descend_lm_batch(fsdf_ctx* ctx, double* x /* [B][nq] */, int32_t B, int32_t iteration_limit, double damping,
+                          double max_step, double tolerance, double n_points, double* value_out,
+                          int32_t* iterations_out, double* damping_out);
+int fsdf_descend_batch(fsdf_ctx* ctx, double* x /* [B][nq] */, int32_t B, int32_t iteration_limit, double rate,
+                       double max_step, double tolerance, const double* divisors, double n_points, double* value_out,
+                       int32_t* iterations_out);
+int fsdf_descend_lm_batch_ref(fsdf_ctx* ctx, double* x /* [B][nq] */, int32_t B, int32_t iteration_limit,
+                              const double* params /* [4] */, double* value_out, int32_t* iterations_out,
+                              double* damping_out);
+int fsdf_descend_batch_ref(fsdf_ctx* ctx, double* x /* [B][nq] */, int32_t B, int32_t iteration_limit,
+                           const double* params /* [4] */, const double* divisors, double* value_out,
+                           int32_t* iterations_out);
+int fsdf_batch_time(fsdf_ctx* ctx, double* total_ms_out, int64_t* launches_out);
+
 /* ---- context ---------------------------------------------------------------- */
 int fsdf_create(fsdf_ctx** out, const fsdf_opts* opts);
 int fsdf_destroy(fsdf_ctx* ctx);

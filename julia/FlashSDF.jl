@@ -501,6 +501,76 @@ function score_time(ctx::Context)
 end
 
 """
+eval_robust at B candidate pose sets in one batch of launches (fsdf_batch_robust_poses): poses is
+12 x S x B; returns (accum (1 + 6S) x B, moments 21 x S x B, weights S x B), each candidate's bit
+for bit what eval_robust returns at its poses. Hull-only scenes; read-only on the context.
+"""
+function batch_robust_poses(ctx::Context, poses::Array{Float64}, S::Integer, B::Integer)
+    accum = zeros(1 + 6S, B)
+    moments = zeros(21, S, B)
+    weights = zeros(S, B)
+    check(ctx.ptr, ccall((:fsdf_batch_robust_poses, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.ptr, poses, Int32(B), accum, moments, weights), "batch_robust_poses")
+    accum, moments, weights
+end
+
+"""
+(cost, gradient, Gauss-Newton Hessian) at B states in one batch of launches (fsdf_batch_states): x is
+nq x B. As score_states, the library runs its own forward kinematics and chain rule, so the context
+needs a mechanism registered through the C interface (this shim registers none: FSDF_ERR_STATE).
+"""
+function batch_states(ctx::Context, x::Array{Float64}, nq::Integer, B::Integer)
+    cost = zeros(B)
+    grad = zeros(nq, B)
+    hess = zeros(nq, nq, B)
+    check(ctx.ptr, ccall((:fsdf_batch_states, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                         ctx.ptr, x, Int32(B), cost, grad, hess), "batch_states")
+    cost, grad, hess
+end
+
+"""
+The Levenberg-Marquardt loop from B starts in lockstep (fsdf_descend_lm_batch_ref: the scalars go by
+reference, as set_loss!'s): x (nq x B) is updated in place. Needs a mechanism registered through C,
+as batch_states.
+"""
+function descend_lm_batch!(ctx::Context, x::Array{Float64}, B::Integer, iteration_limit::Integer, damping::Real,
+                           max_step::Real, tolerance::Real, n_points::Real)
+    params = Float64[damping, max_step, tolerance, n_points]
+    value = zeros(B)
+    iterations = zeros(Int32, B)
+    lambda = zeros(B)
+    check(ctx.ptr, ccall((:fsdf_descend_lm_batch_ref, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                         ctx.ptr, x, Int32(B), Int32(iteration_limit), params, value, iterations, lambda),
+          "descend_lm_batch")
+    value, iterations, lambda
+end
+
+"The NaiveSolver loop from B starts in lockstep (fsdf_descend_batch_ref): x (nq x B) is updated in place; divisors nq."
+function descend_batch!(ctx::Context, x::Array{Float64}, B::Integer, iteration_limit::Integer, rate::Real,
+                        max_step::Real, tolerance::Real, divisors::Vector{Float64}, n_points::Real)
+    params = Float64[rate, max_step, tolerance, n_points]
+    value = zeros(B)
+    iterations = zeros(Int32, B)
+    check(ctx.ptr, ccall((:fsdf_descend_batch_ref, lib), Cint,
+                         (Ptr{Void}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                         ctx.ptr, x, Int32(B), Int32(iteration_limit), params, divisors, value, iterations),
+          "descend_batch")
+    value, iterations
+end
+
+"(summed milliseconds of the batched calls' launches, calls recorded) since the last query (fsdf_batch_time)."
+function batch_time(ctx::Context)
+    ms = Ref{Float64}(0)
+    n = Ref{Int64}(0)
+    check(ctx.ptr, ccall((:fsdf_batch_time, lib), Cint, (Ptr{Void}, Ref{Float64}, Ref{Int64}), ctx.ptr, ms, n),
+          "batch_time")
+    ms[], n[]
+end
+
+"""
 Per-point confidence weights a_i >= 0 (finite) of the resident cloud, in the order of the points
 given to set_points! (fsdf_set_point_weights): every sum of eval_robust carries a_i as a factor
 of point i's terms (cost Σ a ρ, wrench Σ 2 a w d* v, moments Σ a w v vᵀ). They belong to the

@@ -258,6 +258,16 @@ struct fsdf_ctx {
   fsdf::PinnedBuf<double> h_score_poses, h_score_cost;
   std::vector<fsdf::Event> score_ev;
   size_t score_ev_used = 0;
+  // gradients and moments of candidate states (fsdf_batch_robust_poses, fsdf_batch_states and the
+  // lockstep loops over them; batch_api.hip over batch.hip): the batch's poses [B][S][12] and rows
+  // [B][S · 29] on the device and pinned, one slice's posed tables, per-point blocks (k*, d*, ∇d* per
+  // (candidate, point)) and partials; buffers of these calls alone, grown only — a call writes
+  // nothing any other call reads. Timing (fsdf_batch_time) as the scoring calls'.
+  fsdf::DevBuf<double> batch_poses, batch_partials, batch_rows;
+  fsdf::DevBuf<unsigned char> batch_tables, batch_points;
+  fsdf::PinnedBuf<double> h_batch_poses, h_batch_rows;
+  std::vector<fsdf::Event> batch_ev;
+  size_t batch_ev_used = 0;
   // query scratch (fsdf_skin)
   fsdf::DevBuf<unsigned char> q;
   fsdf::DevBuf<double> q64;

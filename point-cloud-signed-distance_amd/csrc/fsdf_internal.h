@@ -232,6 +232,7 @@ hipError_t launch_raycast(int precision, bool cull, const LocalModel& lm, const 
 
 // With cost/order: one extra workgroup also rebuilds order[] (heaviest logical
 // blocks first) from this pass's costs, for the next pass of the same grid.
+constexpr int kTileBlock = 1024;  // the tile reduce's workgroup (reduce_kernels.h reduce_tiles_kernel)
 hipError_t launch_reduce(const double* partials, int nblocks, int len, double* d_accum,
                          hipStream_t s, const uint32_t* cost = nullptr, int32_t* order = nullptr,
                          hipEvent_t ev_stop = nullptr, const int* skip = nullptr);
@@ -355,6 +356,29 @@ hipError_t launch_score(int precision, bool cull, const LocalModel& lm, const vo
                         int64_t n, int B, const float* d_chunk_ws, const double* d_conf, const int32_t* d_perm,
                         int64_t n_surface, int kind, double scale, double* d_partials, double* d_cost,
                         hipStream_t s);
+// ---- gradients and moments of many candidate states (batch.hip) ------------------
+// The rows launch_robust reduces, for nb candidates at once: candidate b's posed
+// table is table b of launch_score_pose's buffer. Two launches and a reduce.
+// launch_batch_eval, grid (score_groups(n), nb): scene_eval of every resident
+// point against table b, its k*, d* and ∇d* — what a pass writes in resident
+// order, the same bits — into candidate b's block of d_points, kBatchPointBytes ·
+// np bytes each: k* [np] i32 | d* [np] f64 | ∇d* [np][3] f64, np =
+// batch_point_stride(n) (n rounded up to whole 64-point chunks).
+// launch_batch_robust, grid (robust_groups(n), nb) then (tiles, nb):
+// robust_kernel's and the tile reduce's statements per candidate (robust_body.inc,
+// reduce_tiles_body.inc) over candidate b's arrays, into d_partials
+// [nb][robust_partials_len(n, S)] and d_rows [nb][S · (moments ? 29 : 8)] — the
+// bits launch_robust gives from the same per-point arrays. n > 0, nb <= 65535,
+// score_fits(lm), robust_fit(S), a valid loss; d_conf, d_perm, n_surface as
+// launch_robust's (the resident cloud's: the same for every candidate).
+inline size_t batch_point_stride(int64_t n) { return (size_t)((n + 63) & ~(int64_t)63); }
+constexpr size_t kBatchPointBytes = 36;
+hipError_t launch_batch_eval(int precision, bool cull, const LocalModel& lm, const void* d_tables, const void* d_pts,
+                             int64_t n, int nb, const float* d_chunk_ws, void* d_points, hipStream_t s);
+hipError_t launch_batch_robust(int precision, bool moments, const void* d_pts, const void* d_points,
+                               const double* d_conf, const int32_t* d_perm, int64_t n_surface,
+                               int64_t n, int S, int nb, int kind, double scale, double* d_partials, double* d_rows,
+                               hipStream_t s);
 // res[i] = src[perm[i]] over n doubles (point_weights.hip: a per-point side array
 // into resident order; an index outside [0, n) reads as 0)
 hipError_t launch_gather_f64(const double* d_src, const int32_t* d_perm, int64_t n, double* d_res, hipStream_t s);

@@ -157,6 +157,17 @@ _PROTOS = {
     "fsdf_score_poses": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "fsdf_score_states": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p]),
     "fsdf_score_time": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
+    "fsdf_batch_robust_poses": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "fsdf_batch_states": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "fsdf_descend_lm_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_double,
+                                        c_void_p, c_void_p, c_void_p]),
+    "fsdf_descend_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_double, c_double, c_double, c_void_p,
+                                     c_double, c_void_p, c_void_p]),
+    "fsdf_descend_lm_batch_ref": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "fsdf_descend_batch_ref": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "fsdf_batch_time": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
 }
 # fsdf_vgh_fn: int (*)(void* user, const double* x, double* f, double* g, double* H)
 VGH_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double),
@@ -544,6 +555,83 @@ class Context:
         cost = np.empty(B, np.float64)
         check(self._lib.fsdf_score_states(self._ctx, ptr(x), B, ptr(cost)), self._ctx, "score_states")
         return cost
+
+    def _state_rows(self, X, who):
+        """X as contiguous f64 [B, nq] (a single state is a batch of one)."""
+        x = np.ascontiguousarray(X, np.float64)
+        nq = getattr(self, "nq", 0)
+        if not nq:  # no mechanism: the library reports FSDF_ERR_STATE (a single state is one row)
+            return x if x.ndim == 2 else x.reshape(1, -1) if x.size else x.reshape(0, 1)
+        if x.ndim == 1:
+            x = x.reshape(-1, nq) if x.size % nq == 0 else x
+        if x.ndim != 2 or x.shape[1] != nq:
+            raise ValueError(f"{who}: X must be [B, {nq}], got shape {x.shape}")
+        return x
+
+    def batch_robust_poses(self, poses, moments: bool = True):
+        """fsdf_batch_robust_poses: poses [B, K, 12] (or [B, K, 3, 4]) ->
+        (accum [B, 1 + 6K], moments [B, K, 21] or None, weights [B, K]): per
+        candidate what eval_robust returns at its poses, bit for bit, all
+        candidates in one batch of launches. Hull-only scenes; read-only on
+        the context."""
+        p = np.ascontiguousarray(poses, np.float64)
+        if p.size % (12 * max(self.K, 1)) != 0:
+            raise ValueError(f"batch_robust_poses: expected [B, {self.K}, 12] poses, got shape {p.shape}")
+        B = p.size // (12 * max(self.K, 1))
+        accum = np.empty((B, 1 + 6 * self.K), np.float64)
+        mom = np.empty((B, self.K, 21), np.float64) if moments else None
+        wts = np.empty((B, self.K), np.float64)
+        check(self._lib.fsdf_batch_robust_poses(self._ctx, ptr(p), B, ptr(accum), ptr(mom), ptr(wts)), self._ctx,
+              "batch_robust_poses")
+        return accum, mom, wts
+
+    def batch_states(self, X, hessian: bool = True):
+        """fsdf_batch_states: states [B, nq] -> (cost [B], grad [B, nq], hess
+        [B, nq, nq] or None): value_gradient_hessian's (c, g, H) under a robust
+        objective at every row, one batch of launches and one synchronisation
+        (set_mechanism first; rigid hull-only scenes)."""
+        x = self._state_rows(X, "batch_states")
+        B, nq = x.shape
+        cost = np.empty(B, np.float64)
+        grad = np.empty((B, nq), np.float64)
+        hess = np.empty((B, nq, nq), np.float64) if hessian else None
+        check(self._lib.fsdf_batch_states(self._ctx, ptr(x), B, ptr(cost), ptr(grad), ptr(hess)), self._ctx,
+              "batch_states")
+        return cost, grad, hess
+
+    def descend_lm_batch(self, X, iteration_limit, damping, max_step, tolerance=0.0, n_points=1.0):
+        """fsdf_descend_lm_batch: descend_lm's host loop for every row of X in
+        lockstep, one batch_states per round. Returns (X, f [B], evaluations
+        [B], final dampings [B])."""
+        x = np.array(self._state_rows(X, "descend_lm_batch"), copy=True)
+        B = x.shape[0]
+        f, it, lam = np.empty(B, np.float64), np.empty(B, np.int32), np.empty(B, np.float64)
+        check(self._lib.fsdf_descend_lm_batch(self._ctx, ptr(x), B, int(iteration_limit), float(damping),
+                                              float(max_step), float(tolerance), float(n_points), ptr(f), ptr(it),
+                                              ptr(lam)), self._ctx, "descend_lm_batch")
+        return x, f, it, lam
+
+    def descend_batch(self, X, iteration_limit, rate, max_step, tolerance=0.0, divisors=None, n_points=1.0):
+        """fsdf_descend_batch: descend's host loop (the NaiveSolver rule) for
+        every row of X in lockstep. Returns (X, f [B], evaluations [B])."""
+        x = np.array(self._state_rows(X, "descend_batch"), copy=True)
+        B = x.shape[0]
+        div = None if divisors is None else np.ascontiguousarray(divisors, np.float64).reshape(-1)
+        if div is not None and div.size != x.shape[1]:
+            raise ValueError("descend_batch: divisors must match a state")
+        f, it = np.empty(B, np.float64), np.empty(B, np.int32)
+        check(self._lib.fsdf_descend_batch(self._ctx, ptr(x), B, int(iteration_limit), float(rate), float(max_step),
+                                           float(tolerance), ptr(div), float(n_points), ptr(f), ptr(it)), self._ctx,
+              "descend_batch")
+        return x, f, it
+
+    def batch_time(self):
+        """(summed milliseconds of the batched calls' launches, the slices
+        recorded: one per call unless the byte budget split its batch) since the
+        last query (profile_pass on)."""
+        ms, n = c_double(0.0), c_int64(0)
+        check(self._lib.fsdf_batch_time(self._ctx, ctypes.byref(ms), ctypes.byref(n)), self._ctx, "batch_time")
+        return ms.value, n.value
 
     def set_point_weights(self, weights):
         """fsdf_set_point_weights: one confidence weight a_i >= 0 (finite) per

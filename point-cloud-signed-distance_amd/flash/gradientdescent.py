@@ -528,6 +528,66 @@ class CostFunctor:
             if device_loop is not None:
                 ctx.set_lm_solver(mode)
 
+    def _batch_states(self, X, who):
+        """X as [B, n_states] for the batched calls, the functor ready for them
+        (native rigid scenes: resident cloud, mechanism, loss)."""
+        if not (self._native and self.rigid):
+            raise NotImplementedError(f"{who}: rigid native scenes only (no RBF skin, no deformation)")
+        if isinstance(X, (list, tuple)) and len(X) and isinstance(X[0], ManipulatorState):
+            X = [flatten(s) for s in X]
+        X = np.ascontiguousarray(X, np.float64)
+        n = num_states(self.manipulator)
+        if X.ndim == 1:
+            X = X.reshape(1, -1) if X.size else X.reshape(0, n)
+        if X.ndim != 2 or X.shape[1] != n:
+            raise ValueError(f"{who}: X must be [B, {n}], got shape {X.shape}")
+        self._ensure_resident()
+        if getattr(self.ctx, "_mechanism_of", None) != (self.manipulator, self.weight):
+            self._register_native()
+        self._assert_loss()
+        return X
+
+    def batch_value_and_gradient(self, X):
+        """(c [B], ∂c/∂x [B, n]) at every row of X in one batch of launches and
+        one synchronisation (fsdf_batch_states, csrc/batch.hip): the robust
+        path's value_and_gradient at each row — the functor's loss, weights and
+        split; least squares as FSDF_LOSS_SQUARE — bit for bit on the same cloud
+        layout. Native rigid scenes; read-only on the resident cloud."""
+        X = self._batch_states(X, "batch_value_and_gradient")
+        c, g, _ = self.ctx.batch_states(X, hessian=False)
+        return c, g
+
+    def batch_value_gradient_hessian(self, X):
+        """(c [B], ∂c/∂x [B, n], the Gauss-Newton Hessians [B, n, n]) at every
+        row of X, as batch_value_and_gradient; the same (c, g) bits."""
+        X = self._batch_states(X, "batch_value_gradient_hessian")
+        return self.ctx.batch_states(X, hessian=True)
+
+    def descend_batch(self, X, iteration_limit, rate, max_step, tolerance=0.0, divisors=None, n_points=1.0):
+        """descend's host loop (the NaiveSolver rule) from every row of X in
+        lockstep, one batched evaluation and one synchronisation per iteration
+        for all of them (fsdf_descend_batch). Returns (X, f [B], iterations
+        [B])."""
+        X = self._batch_states(X, "descend_batch")
+        return self.ctx.descend_batch(X, iteration_limit, rate, max_step, tolerance, divisors, n_points)
+
+    def descend_lm_batch(self, X, iteration_limit, damping, max_step, tolerance=0.0, n_points=1.0,
+                         prior_weight=None):
+        """descend_lm's host loop from every row of X in lockstep
+        (fsdf_descend_lm_batch): one batched (c, g, H) per round over the rows
+        still running. prior_weight as descend_lm's, about each row's own start;
+        it holds for this call alone. Returns (X, f [B], evaluations [B], final
+        dampings [B])."""
+        X = self._batch_states(X, "descend_lm_batch")
+        ctx = self.ctx
+        try:
+            if prior_weight is not None:
+                ctx.set_lm_prior(prior_weight)
+            return ctx.descend_lm_batch(X, iteration_limit, damping, max_step, tolerance, n_points)
+        finally:
+            if prior_weight is not None:
+                ctx.set_lm_prior(None)
+
     def per_point(self, x):
         """(d*, k*, ∇d*) for every sensed point at configuration x."""
         return self._pass(x, per_point=True)[2]

@@ -386,11 +386,55 @@ def select_candidates(scores, keep: int) -> np.ndarray:
     return np.array(order[:keep], np.int64)
 
 
-def _multi_start_on(cost, n_points: int, candidates, keep, solver, callback):
+def _refine_batched(cost, n_points: int, X, solver):
+    """The kept candidates X [keep, n_states] refined by one lockstep loop
+    (CostFunctor.descend_batch / descend_lm_batch, by the solver's type) with
+    _optimize's arguments; the refined objectives come from one score call.
+    Returns (refined states, their objectives, the final dampings or None). The
+    lockstep loops are host loops: a LevenbergMarquardt's device_loop does not
+    apply (None, False and True are ignored; "require" is refused by
+    _check_batched)."""
+    n = max(n_points, 1)
+    lam = None
+    if type(solver) is NaiveSolver:
+        div = solver.precondition_divisors
+        if div is not None:  # NaiveSolver broadcasts the divisors; fsdf_descend_batch takes one per entry
+            div = np.broadcast_to(np.asarray(div, np.float64), (X.shape[1],)).copy()
+        R, _, its = cost.descend_batch(X, solver.iteration_limit, solver.rate, solver.max_step,
+                                       solver.gradient_convergence_tolerance, div, n)
+    else:
+        R, _, its, lam = cost.descend_lm_batch(X, solver.iteration_limit, solver.damping, solver.max_step,
+                                             solver.gradient_convergence_tolerance, n,
+                                             prior_weight=solver.prior_weight)
+    solver.iterations = int(np.max(its)) if len(its) else 0
+    R = np.asarray(R, np.float64)
+    return [R[i] for i in range(R.shape[0])], np.asarray(cost.score(R), np.float64).reshape(-1), lam
+
+
+def _check_batched(cost, solver, callback):
+    """multi_start(batched=True)'s conditions: the lockstep loops are the two
+    native solver loops without a per-evaluation callback (cost None: the scene
+    is checked later, once the functor exists)."""
+    if callback is not None:
+        raise ValueError("multi_start: batched=True takes no callback (the candidates advance in lockstep)")
+    if type(solver) is not NaiveSolver and type(solver) is not LevenbergMarquardt:
+        raise ValueError(f"multi_start: batched=True refines with NaiveSolver or LevenbergMarquardt, not "
+                         f"{type(solver).__name__}")
+    if getattr(solver, "device_loop", None) == "require":
+        raise ValueError('multi_start: batched=True runs host loops around a batched device evaluation; a '
+                         'LevenbergMarquardt(device_loop="require") cannot be honoured')
+    if cost is not None and not (getattr(cost, "_native", False) and getattr(cost, "rigid", True)):
+        raise ValueError("multi_start: batched=True needs a native rigid scene (no RBF skin, no deformation)")
+
+
+def _multi_start_on(cost, n_points: int, candidates, keep, solver, callback, batched: bool = False):
     """multi_start over a functor whose cloud is resident and whose loss and
-    weights are set: score, select, refine each kept candidate with _optimize,
-    return the refined state of least final objective (ties: the better-scored
-    candidate; a NaN objective last)."""
+    weights are set: score, select, refine each kept candidate with _optimize
+    (batched: all of them by one lockstep loop, _refine_batched), return the
+    refined state of least final objective (ties: the better-scored candidate;
+    a NaN objective last)."""
+    if batched:
+        _check_batched(cost, solver, callback)
     X = np.ascontiguousarray(candidates, np.float64)
     if X.ndim != 2 or X.shape[0] < 1:
         raise ValueError(f"multi_start: candidates must be [B >= 1, n_states], got shape {X.shape}")
@@ -398,13 +442,18 @@ def _multi_start_on(cost, n_points: int, candidates, keep, solver, callback):
     if scores.size != X.shape[0]:
         raise ValueError(f"multi_start: {scores.size} scores for {X.shape[0]} candidates")
     kept = select_candidates(scores, keep)
-    refined, refined_costs = [], []
-    for b in kept:
-        x = _optimize(cost, n_points, X[b], callback, solver)
-        refined.append(np.asarray(x, np.float64))
-        refined_costs.append(float(cost(x)))
+    refined, refined_costs, dampings = [], [], None
+    if batched:
+        refined, refined_costs, dampings = _refine_batched(cost, n_points, np.ascontiguousarray(X[kept]), solver)
+    else:
+        for b in kept:
+            x = _optimize(cost, n_points, X[b], callback, solver)
+            refined.append(np.asarray(x, np.float64))
+            refined_costs.append(float(cost(x)))
     refined_costs = np.array(refined_costs, np.float64)
     j = int(select_candidates(refined_costs, 1)[0])
+    if dampings is not None:  # (batched LevenbergMarquardt: the chosen candidate's, as one optimize leaves it)
+        solver.final_damping = float(dampings[j])
     info = {"scores": scores, "kept": kept, "refined_costs": refined_costs, "chosen": int(kept[j]),
             "refined": np.array(refined)}
     return refined[j], info
@@ -412,7 +461,7 @@ def _multi_start_on(cost, n_points: int, candidates, keep, solver, callback):
 
 def multi_start(manipulator: Manipulator, sensed_points, candidates, keep: int = 1, solver=None, loss=None,
                 weights=None, voxel=None, device: int = 0, precision: int = 64, callback=None,
-                robust_loops: bool = False):
+                robust_loops: bool = False, batched: bool = False):
     """A start in the right basin, found rather than given: score every
     candidate state against the cloud in one batch of launches
     (CostFunctor.score, fsdf_score_states), keep the `keep` lowest, refine each
@@ -428,8 +477,22 @@ def multi_start(manipulator: Manipulator, sensed_points, candidates, keep: int =
     index — for the scores and for the refined costs (in `kept` order) alike.
     sensed_points, loss, weights, voxel, device, precision, callback and solver
     and robust_loops are estimate_state's (a DepthFrame and a VoxelGrid included); candidates is
-    [B, n_states] (candidates_around draws them). Native rigid scenes."""
+    [B, n_states] (candidates_around draws them). Native rigid scenes.
+    batched (False: the path above, untouched): the kept candidates are refined
+    together by one lockstep loop (CostFunctor.descend_batch for a NaiveSolver,
+    descend_lm_batch for a LevenbergMarquardt: one batched evaluation and one
+    synchronisation per iteration for all of them) and their refined objectives
+    come from one score call; info keeps its keys and the selection rule is the
+    same. A callback, any other solver, a LevenbergMarquardt with
+    device_loop="require" (the lockstep loops are host loops; any other
+    device_loop is ignored) or a non-native scene raises ValueError. Afterwards
+    solver.iterations is the largest evaluation count among the kept candidates
+    and a LevenbergMarquardt's final_damping the chosen candidate's.
+    On least squares the refined objectives differ from the default path's in
+    their last bits (the batched evaluation reduces in the robust path's order)."""
     solver = solver or _default_solver(manipulator)
+    if batched:  # (before anything is uploaded; the scene is checked once the functor exists)
+        _check_batched(None, solver, callback)
     X = np.ascontiguousarray(candidates, np.float64)
     if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] != num_states(manipulator):
         raise ValueError(f"multi_start: candidates must be [B >= 1, {num_states(manipulator)}], got shape {X.shape}")
@@ -451,7 +514,7 @@ def multi_start(manipulator: Manipulator, sensed_points, candidates, keep: int =
     w = _frame_weights(weights, pts)
     if w is not None:
         cost.set_point_weights(w)
-    return _multi_start_on(cost, getattr(cost, "n_divisor", cost.n_points), X, keep, solver, callback)
+    return _multi_start_on(cost, getattr(cost, "n_divisor", cost.n_points), X, keep, solver, callback, batched)
 
 
 def notebook_frame_solver(manipulator):
@@ -528,15 +591,18 @@ class Tracker:
         return x
 
     def relocalize(self, sensed_points, candidates=None, sigma=0.3, count: int = 64, keep: int = 2, seed=0,
-                   solver=None, callback=None, weights=None, voxel="tracker"):
+                   solver=None, callback=None, weights=None, voxel="tracker", batched: bool = False):
         """Find the state again (a first frame, or after an occlusion or a
         dropped frame): make the frame's cloud resident as step does, run
         multi_start's search on the Tracker's own CostFunctor around its current
         state — candidates, or candidates_around(state, sigma, count, seed) —
         and adopt the result. Returns (x, info) as multi_start. solver: the
         refinement's solver (default: estimate_state's, 30 iterations; the
-        Tracker's own frame solver takes single steps). step itself never calls
-        this: recovery is the caller's decision."""
+        Tracker's own frame solver takes single steps). batched: multi_start's
+        (the kept candidates refined by one lockstep loop). step itself never
+        calls this: recovery is the caller's decision."""
+        if batched:  # (before the cloud is swapped)
+            _check_batched(self.cost, solver or _default_solver(self.manipulator), callback)
         grid = self.voxel if isinstance(voxel, str) and voxel == "tracker" else voxel
         if isinstance(sensed_points, DepthFrame) or grid is not None:
             pts = lambda: self.cost.sensed_points  # noqa: E731 (formed when asked for)
@@ -556,7 +622,7 @@ class Tracker:
         if w is not None:
             self.cost.set_point_weights(w)
         x, info = _multi_start_on(self.cost, getattr(self.cost, "n_divisor", self.cost.n_points), candidates, keep,
-                                  solver or _default_solver(self.manipulator), callback)
+                                  solver or _default_solver(self.manipulator), callback, batched)
         unflatten(self.state, x)
         return x, info
 
